@@ -14,7 +14,14 @@ N > 1: one process per GPU (torch.distributed, RCCL), rank r owns a contiguous r
 N × size-gb file (weak scaling) and loads only its byte range + halo (sbam/dist.py).  `--gpus N` without a
 torchrun environment spawns the N ranks itself (torch.distributed.run) before anything touches the GPU.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (largest average device time),
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline
+(`value`, `ms_per_step`, the workload's `config`, and the per-kernel `kernel_ms` the steps themselves record);
+`--dump-outputs DIR` also writes what the last timed step returned (Counts and the split rows) as DIR/<name>.npy.
+Everything below takes runs or checks of its own and is added to the line only with `--full`: `parity` (record
+counts and the oracle-pinned digests), `roofline` / `stage_rooflines`, `hbm_copy_peak`, `e2e_h2d`,
+`with_chain_proof` and `cpu_baseline`.
+
+`roofline` is for the dominant kernel (largest average device time),
 measured with HIP events on the library's stream over the timed steps; `e2e_h2d` is the same step from
 pinned host memory (host → device copies inside the timed step, overlapped with the kernels of the previous
 window); `cpu_baseline` times the CPU oracle (oracle/, a C restatement of the reference — the Scala/Spark
@@ -195,6 +202,17 @@ def cpu_baseline_load_reads(args, sample_mb: float, threads: int, split_size: in
                       f"column decode), {wall:.2f} s wall"}
 
 
+def dump_outputs(out_dir: str, parts):
+    """--dump-outputs: what the last timed step returned to its caller (sdist.ShardResult; `parts` is the
+    per-rank list after the gather when N > 1, whose first entry holds the merged Counts), one DIR/<name>.npy per
+    field in float64 (every value is an integer far below 2^53, so the conversion is exact).  A few hundred KB."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "counts.npy"), np.asarray(parts[0].counts, np.float64))
+    for name in ("first_block_pos", "first_offset", "nonempty", "n_records"):
+        np.save(os.path.join(out_dir, name + ".npy"),
+                np.concatenate([np.asarray(getattr(p, name), np.float64).ravel() for p in parts]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -208,9 +226,9 @@ def main():
     ap.add_argument("--threads", type=int, default=0, help="host threads (generator, CPU baseline); 0 = the host share")
     ap.add_argument("--cpu-sample-mb", type=float, default=2000.0,
                     help="compressed MB of the same synthetic file timed on the CPU oracle (~10 s at 16 threads)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--e2e-windows", type=int, default=6,
-                    help="windows of the pinned-host → results measurement (0 = skip it)")
+                    help="with --full: windows of the pinned-host → results measurement (0 = skip it)")
     ap.add_argument("--e2e-steps", type=int, default=3)
     ap.add_argument("--seed", type=lambda x: int(x, 0), default=0x5EEDBA11)
     ap.add_argument("--workload", choices=["full-check", "load-reads"], default="full-check",
@@ -232,7 +250,16 @@ def main():
     ap.add_argument("--dist-backend", default="nccl",
                     help="nccl (RCCL, the product path); gloo only to rehearse N ranks on one GPU (--device)")
     ap.add_argument("--device", type=int, default=None, help="GPU index (default LOCAL_RANK)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: the parity properties and "
+                         "oracle-pinned digests, rooflines, the HBM copy peak, the pinned-host measurement, the "
+                         "forced-proof loadReads steps and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (Counts words and the per-split rows) as "
+                         "DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -372,6 +399,56 @@ def main():
     sync()
     elapsed = max_over_ranks(time.perf_counter() - t0)
 
+    # --- the headline: everything in it is in hand when the timed steps end
+    U, nblocks = last["U"], last["nblocks"]
+    avg = {k: tot_ms[k] / args.steps for k in kernels}
+    retries = int(shard.retries if W == 1 else sum(c.retries for c in pipe.ctx if c))
+    fc = args.workload == "full-check"
+    line = {
+        "metric": "compressed BAM GB/s for compute-splits + full-check (whole node, 1/2/4/8 GPU)" if fc else
+                  "compressed BAM GB/s for loadReads record decode (whole node, 1/2/4/8 GPU)",
+        "value": round(s.size * args.steps / elapsed / 1e9, 3),
+        "unit": "GB/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": data_desc(args, s),
+        "config": {"workload": ("%s %.0f GB %s BAM per GPU: " % (
+                               "Real-data" if args.real else "Synthetic", args.size_gb,
+                               "5k.bam-tiled" if args.real else
+                               ("Illumina-like" if args.read_len == 150 else "long-read" if args.read_len == 0
+                                else f"{args.read_len} bp") + ("" if args.level == 6 else f" zlib-{args.level}"))) +
+                               ("compute-splits @ %g MiB + full-check of every uncompressed offset" % args.split_mb
+                                if fc else "loadReads @ %g MiB splits: records decoded into device columns"
+                                % args.split_mb),
+                   "file_gb": round(s.size / 1e9, 3), "uncompressed_gb_per_gpu": round(U / 1e9, 3),
+                   "records": s.n_records, "blocks_per_gpu": nblocks, "split_mb": args.split_mb,
+                   "windows_per_gpu": W, "parallelism": f"shard{world}",
+                   "halo_retries": retries,
+                   "tiles": min(args.tiles, s.copies), "setup_s": round(setup_s, 1),
+                   **({"contigs": len(s.contig_lengths)} if args.contigs else {})},
+        "uncompressed_gbps": round(U * world * args.steps / elapsed / 1e9, 3),
+        "kernel_ms": {k: round(v, 3) for k, v in avg.items()},
+    }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gathered["all"] if "all" in gathered else [res])
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if shard is not None:
+            shard.close()
+        if pipe is not None:
+            pipe.drop_prefetch()
+            pipe.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     # --- size-independent parity properties of the last step (full sizes; fixtures cover exactness)
     counts = sdist.unpack_counts(res.counts)
     n_rec = int(res.n_records.sum())
@@ -409,12 +486,10 @@ def main():
     # k_check_bits (full-check record-0 pass over the interior tiles: reads U, writes the U/8 PASS0 bitmap),
     # k_inflate_decode (reads the C payload; its token stream is an internal intermediate) and
     # k_inflate_resolve (writes U; tokens internal).
-    U, nblocks = last["U"], last["nblocks"]
     if W == 1:  # the compressed payload bytes decode reads (block table of the shard, outside the timed region)
         comp_payload = int(shard.f.blocks()[1].astype(np.int64).sum())
     else:
         comp_payload = plan.owned_hi - plan.lo
-    avg = {k: tot_ms[k] / args.steps for k in kernels}
     alg = {"check_pass0": U + U // 8, "inflate_decode": comp_payload, "inflate_resolve": U}
     names = {"check_pass0": "k_check_bits", "inflate_decode": "k_inflate_decode",
              "inflate_resolve": "k_inflate_resolve"}
@@ -457,7 +532,7 @@ def main():
     # --- pinned host → results (SURVEY §8(d) "with H2D"): the same step with the shard's compressed bytes in
     # pinned host memory, streamed in `e2e_windows` windows through two contexts (window w+1's copy overlaps
     # window w's kernels; window 0's copy is not overlapped).
-    retries = int(shard.retries if W == 1 else sum(c.retries for c in pipe.ctx if c))
+    line["config"]["halo_retries"] = int(shard.retries if W == 1 else sum(c.retries for c in pipe.ctx if c))
     e2e = None
     if args.e2e_windows > 0 and W == 1 and args.workload == "full-check":
         if shard is not None:
@@ -506,38 +581,7 @@ def main():
         except Exception as e:
             log(f"copy peak failed: {e!r}")
             cpk = None
-        value = s.size * args.steps / elapsed / 1e9
-        fc = args.workload == "full-check"
-        line = {
-            "metric": "compressed BAM GB/s for compute-splits + full-check (whole node, 1/2/4/8 GPU)" if fc else
-                      "compressed BAM GB/s for loadReads record decode (whole node, 1/2/4/8 GPU)",
-            "value": round(value, 3),
-            "unit": "GB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": data_desc(args, s),
-            "config": {"workload": ("%s %.0f GB %s BAM per GPU: " % (
-                                   "Real-data" if args.real else "Synthetic", args.size_gb,
-                                   "5k.bam-tiled" if args.real else
-                                   ("Illumina-like" if args.read_len == 150 else "long-read" if args.read_len == 0
-                                    else f"{args.read_len} bp") + ("" if args.level == 6 else f" zlib-{args.level}"))) +
-                                   ("compute-splits @ %g MiB + full-check of every uncompressed offset" % args.split_mb
-                                    if fc else "loadReads @ %g MiB splits: records decoded into device columns"
-                                    % args.split_mb),
-                       "file_gb": round(s.size / 1e9, 3), "uncompressed_gb_per_gpu": round(U / 1e9, 3),
-                       "records": s.n_records, "blocks_per_gpu": nblocks, "split_mb": args.split_mb,
-                       "windows_per_gpu": W, "parallelism": f"shard{world}",
-                       "halo_retries": retries,
-                       "tiles": min(args.tiles, s.copies), "setup_s": round(setup_s, 1),
-                       **({"contigs": len(s.contig_lengths)} if args.contigs else {})},
-            "uncompressed_gbps": round(U * world * args.steps / elapsed / 1e9, 3),
-            "kernel_ms": {k: round(v, 3) for k, v in avg.items()},
+        line.update({
             "roofline": {"bound": "hbm", "kernel": names[dom], "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                          "traffic": traffic["hbm_bytes_per_launch"] if traffic else None,
@@ -556,7 +600,7 @@ def main():
             **({"with_chain_proof": proof} if proof else {}),
             "cpu_baseline": cpu,
             "parity": parity,
-        }
+        })
         print(json.dumps(line), flush=True)
     if shard is not None:
         shard.close()

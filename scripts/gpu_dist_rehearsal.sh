@@ -4,5 +4,5 @@ set -o pipefail
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-timeout -k 10 500 python bench.py --gpus 2 --steps 3 --warmup 1 --size-gb 4 --dist-backend gloo --device 0 \
+timeout -k 10 500 python bench.py --full --gpus 2 --steps 3 --warmup 1 --size-gb 4 --dist-backend gloo --device 0 \
   --no-cpu-baseline --e2e-windows 0 > gpurun_out/bench_n2_rehearsal.log 2>&1 || exit 1

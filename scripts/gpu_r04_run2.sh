@@ -10,4 +10,4 @@ for b in build build_r2nd build_r4 build_r4nd; do
   SBAM_LIB=$PWD/spark-bam_amd/$b/libsbam.so timeout -k 10 300 python -u tools/bench_kernels.py --size-gb 10 --only inflate --reps 3 > $OUT/kern_$b.log 2>&1 || exit 2
 done
 timeout -k 10 300 python -u tools/wave_stats.py 2 > $OUT/wave_stats.log 2>&1 || exit 3
-timeout -k 10 500 python -u bench.py > $OUT/bench.log 2>&1 || exit 4
+timeout -k 10 500 python -u bench.py --full > $OUT/bench.log 2>&1 || exit 4

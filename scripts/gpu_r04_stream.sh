@@ -5,6 +5,6 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 OUT=gpurun_out/stream
 mkdir -p $OUT
-timeout -k 10 300 python -u bench.py --workload load-reads > $OUT/bench_load_reads.log 2>&1 || exit 1
-SBAM_PIPE_DEBUG=1 SBAM_LOG_GROW=1 timeout -k 10 400 python -u bench.py --size-gb 30 --windows 3 --steps 3 --warmup 1 --no-cpu-baseline --e2e-windows 0 > $OUT/bench_fc_30g_win3.log 2>&1 || exit 2
-SBAM_LOG_GROW=1 timeout -k 10 500 python -u bench.py --size-gb 100 --windows 10 --workload load-reads --steps 2 --warmup 1 --no-cpu-baseline --e2e-windows 0 > $OUT/bench_load_reads_100g_win10.log 2>&1 || exit 3
+timeout -k 10 300 python -u bench.py --full --workload load-reads > $OUT/bench_load_reads.log 2>&1 || exit 1
+SBAM_PIPE_DEBUG=1 SBAM_LOG_GROW=1 timeout -k 10 400 python -u bench.py --full --size-gb 30 --windows 3 --steps 3 --warmup 1 --no-cpu-baseline --e2e-windows 0 > $OUT/bench_fc_30g_win3.log 2>&1 || exit 2
+SBAM_LOG_GROW=1 timeout -k 10 500 python -u bench.py --full --size-gb 100 --windows 10 --workload load-reads --steps 2 --warmup 1 --no-cpu-baseline --e2e-windows 0 > $OUT/bench_load_reads_100g_win10.log 2>&1 || exit 3

@@ -10,6 +10,6 @@ for b in ${LIBS:-build build_base build build_base}; do
   SBAM_LIB=$PWD/spark-bam_amd/$b/libsbam.so timeout -k 10 300 python -u tools/bench_kernels.py --size-gb 10 --only ${ONLY:-check_full,check_eager} --reps 5 >> $OUT/kern_$b.log 2>&1 || exit 2
 done
 if [ -n "$LONG" ]; then
-  timeout -k 10 400 python -u bench.py --read-len 0 --e2e-windows 0 --no-cpu-baseline > $OUT/bench_long_full.log 2>&1 || exit 3
-  timeout -k 10 400 python -u bench.py --read-len 0 --e2e-windows 0 --workload load-reads --no-cpu-baseline > $OUT/bench_long_load.log 2>&1 || exit 4
+  timeout -k 10 400 python -u bench.py --full --read-len 0 --e2e-windows 0 --no-cpu-baseline > $OUT/bench_long_full.log 2>&1 || exit 3
+  timeout -k 10 400 python -u bench.py --full --read-len 0 --e2e-windows 0 --workload load-reads --no-cpu-baseline > $OUT/bench_long_load.log 2>&1 || exit 4
 fi
