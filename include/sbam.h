@@ -33,6 +33,7 @@ extern "C" {
 #define SBAM_ERR_HIP 7            /* HIP runtime failure (device, allocation, launch)                       */
 #define SBAM_ERR_STATE 8          /* stage called out of order (e.g. check before inflate)                  */
 #define SBAM_ERR_HALO 9           /* a check needed bytes past a shard's loaded range (grow the halo)       */
+#define SBAM_ERR_RECORD 10        /* variable-length fields overrun block_size; error.position = record offset */
 
 typedef struct sbam_ctx sbam_ctx;
 
@@ -242,9 +243,65 @@ int sbam_get_record_columns(sbam_ctx *ctx, int64_t i0, int64_t n, const sbam_rec
 /* Device pointers of the last sbam_load_records' columns (for in-process GPU consumers; no copy). */
 int sbam_record_columns_device(sbam_ctx *ctx, sbam_record_columns *dev, int64_t *n_records);
 
+/* ---- variable-length fields: the rest of the SAMRecord (SAM spec §4.2) ------------------------------------ */
+
+/* Field mask of sbam_load_record_fields. */
+#define SBAM_FIELD_NAME 1u
+#define SBAM_FIELD_CIGAR 2u
+#define SBAM_FIELD_SEQ 4u
+#define SBAM_FIELD_QUAL 8u
+#define SBAM_FIELD_AUX 16u
+
+/* CSR columns of a batch of n records: every *_off has n + 1 int64 entries (exclusive prefix sums, [n] = total).
+ *   name   read_name bytes without the trailing NUL (l_read_name - 1; 0 when l_read_name <= 1)   name_off
+ *   cigar  the raw uint32 ops (len << 4 | op)                                                    cigar_off (in ops)
+ *   seq    one ASCII byte per base, "=ACMGRSVTWYHKDBN"[nibble], high nibble first                 seq_off
+ *   qual   the raw phred bytes (0xFF kept as is)                                                 seq_off (shared)
+ *   aux    the raw tag bytes from the end of qual to offset + 4 + block_size                     aux_off */
+typedef struct {
+  int64_t *name_off;
+  uint8_t *name;
+  int64_t *cigar_off;
+  uint32_t *cigar;
+  int64_t *seq_off;
+  uint8_t *seq;
+  uint8_t *qual;
+  int64_t *aux_off;
+  uint8_t *aux;
+} sbam_record_fields;
+
+typedef struct {
+  int64_t name_bytes;
+  int64_t cigar_ops;
+  int64_t seq_bases;
+  int64_t aux_bytes;
+} sbam_record_field_totals;
+
+/* Decode the variable-length fields selected by `fields` (SBAM_FIELD_*) of records [i0, i0 + n) of the last
+ * sbam_load_records into device columns owned by ctx (a grow-only arena; valid until the next call, load, reset or
+ * close): what htsjdk BAMRecordCodec.decode reads behind RecordStream.scala:16-33 (SAM spec §4.2: read_name, cigar,
+ * seq, qual, tags), for the SAMRecords of loadReads (CanLoadBam.scala:221-241, 348-352).  The batch bounds the memory:
+ * the decoded columns of a whole file are about 1.3x its uncompressed size.  All four offset columns are always
+ * produced; *totals (may be NULL) receives their last entries.  A record whose l_seq is negative, whose fields need
+ * more than block_size bytes, or that ends past the stream is SBAM_ERR_RECORD with error.position = its stream
+ * offset (the first such record of the batch; nothing is decoded).  SBAM_ERR_STATE without loaded records,
+ * SBAM_ERR_ARG for a range outside them or an empty or unknown mask; n = 0 is SBAM_OK with zero totals. */
+int sbam_load_record_fields(sbam_ctx *ctx, int64_t i0, int64_t n, uint32_t fields, sbam_record_field_totals *totals);
+
+/* Copy the columns of the last sbam_load_record_fields into caller-owned host buffers sized from its totals (the
+ * SAMRecord accessors getReadName / getCigar / getReadBases / getBaseQualities / getAttributes of BAMRecordCodec.decode,
+ * SAM spec §4.2).  NULL members are not copied; a data member of a field that was not selected is SBAM_ERR_ARG. */
+int sbam_get_record_fields(sbam_ctx *ctx, const sbam_record_fields *out);
+
+/* Device pointers of the last sbam_load_record_fields' columns and its batch (for in-process GPU consumers; no copy;
+ * the device-side form of BAMRecordCodec.decode's variable-length part, SAM spec §4.2).  The data pointer of a field
+ * that was not selected is NULL. */
+int sbam_record_fields_device(sbam_ctx *ctx, sbam_record_fields *dev, int64_t *i0, int64_t *n);
+
 /* ---- timing support for bench/profiling -------------------------------------------------------- */
 /* Device time (ms, HIP events on the library's stream) of the most recent launch of a named kernel
- * family: "scan", "inflate", "check_full", "check_eager", "records", "load_records". Returns -1 if none. */
+ * family: "scan", "inflate", "check_full", "check_eager", "records", "load_records", "record_fields" (the gather of
+ * sbam_load_record_fields; "record_field_sizes": its sizes and scan). Returns -1 if none. */
 double sbam_last_kernel_ms(sbam_ctx *ctx, const char *kernel);
 
 #ifdef __cplusplus

@@ -99,6 +99,12 @@ struct sbam_ctx {
   size_t rcols_cap = 0;
   RecordColumnsDev rcols{};
   int64_t n_loaded = -1;
+  // variable-length fields of the last sbam_load_record_fields: offsets + scan scratch, and the data arena
+  uint8_t *d_foff = nullptr, *d_fdata = nullptr;
+  size_t foff_cap = 0, fdata_cap = 0;
+  sbam_record_fields fdev{};  // device pointers (data of unselected fields: null)
+  int64_t f_i0 = 0, f_n = -1;
+  sbam_record_field_totals f_tot{};
   // small device scratch
   int64_t *d_small = nullptr;  // 64 int64
   unsigned long long *d_counts = nullptr;
@@ -350,6 +356,8 @@ void sbam_close(sbam_ctx *c) {
   dfree(c->d_sb);
   dfree(c->d_roff);
   dfree(c->d_rcols);
+  dfree(c->d_foff);
+  dfree(c->d_fdata);
   for (auto &kv : c->ev) {
     (void)hipEventDestroy(kv.second.first);
     (void)hipEventDestroy(kv.second.second);
@@ -472,6 +480,7 @@ int sbam_reset(sbam_ctx *c) {
   c->inflate_slow = -1;
   c->bm_valid = false;
   c->n_loaded = -1;
+  c->f_n = -1;
   c->err = sbam_error{};
   return SBAM_OK;
 }
@@ -1268,6 +1277,7 @@ int sbam_load_records(sbam_ctx *c, const sbam_split_args *a, int64_t first, int6
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   c->n_loaded = -1;
+  c->f_n = -1;
   std::vector<int64_t> xs, xe, cnt;
   rc = split_starts(c, a, first, count, xs, xe);
   if (rc) return rc;
@@ -1341,6 +1351,122 @@ int sbam_record_columns_device(sbam_ctx *c, sbam_record_columns *d, int64_t *n_r
   *d = sbam_record_columns{c->d_roff, k.block_pos, k.block_off, k.block_size, k.ref_id, k.pos,
                            k.bin_mq_nl, k.flag_nc, k.l_seq, k.next_ref_id, k.next_pos, k.tlen};
   if (n_records) *n_records = c->n_loaded;
+  return SBAM_OK;
+}
+
+// ---- variable-length fields (SAM spec §4.2; htsjdk BAMRecordCodec.decode behind RecordStream.scala:16-33) ----
+int sbam_load_record_fields(sbam_ctx *c, int64_t i0, int64_t n, uint32_t fields, sbam_record_field_totals *totals) {
+  if (!c) return SBAM_ERR_ARG;
+  if (c->n_loaded < 0 || c->L < 0) return set_err(c, SBAM_ERR_STATE, "sbam_load_records has not run");
+  constexpr uint32_t kAll = SBAM_FIELD_NAME | SBAM_FIELD_CIGAR | SBAM_FIELD_SEQ | SBAM_FIELD_QUAL | SBAM_FIELD_AUX;
+  if (i0 < 0 || n < 0 || i0 + n > c->n_loaded)
+    return set_err(c, SBAM_ERR_ARG, "records [%lld, %lld) outside the %lld loaded", (long long)i0, (long long)(i0 + n),
+                   (long long)c->n_loaded);
+  if (fields == 0 || (fields & ~kAll)) return set_err(c, SBAM_ERR_ARG, "field mask 0x%x", (unsigned)fields);
+  HIPCHK(c, hipSetDevice(c->device));
+  c->f_n = -1;
+  c->fdev = sbam_record_fields{};
+  c->f_tot = sbam_record_field_totals{};
+  if (totals) *totals = c->f_tot;
+  if (n == 0) {
+    c->f_i0 = i0;
+    c->f_n = 0;
+    return SBAM_OK;
+  }
+  // offsets arena: four int64 columns of n + 1, the scan's per-workgroup sums, first bad record + four totals
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t ostride = up((size_t)(n + 1) * 8), nblk = (size_t)field_size_blocks(n);
+  HIPCHK(c, ensure(&c->d_foff, &c->foff_cap, 4 * ostride + up(4 * nblk * 8) + 256));
+  int64_t *off[4];
+  for (int f = 0; f < 4; f++) off[f] = reinterpret_cast<int64_t *>(c->d_foff + f * ostride);
+  int64_t *bsum = reinterpret_cast<int64_t *>(c->d_foff + 4 * ostride);
+  int64_t *small = reinterpret_cast<int64_t *>(c->d_foff + 4 * ostride + up(4 * nblk * 8));  // [0] bad, [1..4] totals
+  const RecordColumnsDev &k = c->rcols;
+  const FieldSizesArgs sa{c->d_roff + i0, k.block_size + i0, k.bin_mq_nl + i0, k.flag_nc + i0, k.l_seq + i0, n, c->L};
+  {
+    Timer t(c, "record_field_sizes");
+    HIPCHK(c, launch_field_sizes(sa, bsum, FieldOffsets{off[0], off[1], off[2], off[3]},
+                                 reinterpret_cast<unsigned long long *>(small), small + 1, c->stream));
+  }
+  int64_t h[5];
+  HIPCHK(c, hipMemcpyAsync(h, small, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (h[0] != -1) {  // the gather is not launched: it reads only records that passed
+    int64_t x = -1;
+    HIPCHK(c, hipMemcpy(&x, c->d_roff + i0 + h[0], 8, hipMemcpyDeviceToHost));
+    c->err.position = x;
+    return set_err(c, SBAM_ERR_RECORD, "record %lld at %lld: variable-length fields overrun block_size",
+                   (long long)(i0 + h[0]), (long long)x);
+  }
+  const sbam_record_field_totals tot{h[1], h[2], h[3], h[4]};
+  // data arena: the selected columns, each 256-B aligned and padded to the gather's 8-byte stores
+  const struct { uint32_t bit; int64_t bytes; int off; int sh; } col[5] = {
+      {SBAM_FIELD_NAME, tot.name_bytes, 0, 0}, {SBAM_FIELD_CIGAR, 4 * tot.cigar_ops, 1, 2},
+      {SBAM_FIELD_SEQ, tot.seq_bases, 2, 0},   {SBAM_FIELD_QUAL, tot.seq_bases, 2, 0},
+      {SBAM_FIELD_AUX, tot.aux_bytes, 3, 0}};
+  // (behind each: the gather's per-tile record ranges)
+  size_t need = 0, at[5], tiles_at[5];
+  for (int f = 0; f < 5; f++) {
+    at[f] = tiles_at[f] = need;
+    if (!(fields & col[f].bit)) continue;
+    need += up((size_t)col[f].bytes + 8);
+    tiles_at[f] = need;
+    need += up((size_t)field_gather_tiles(col[f].bytes) * 16);
+  }
+  HIPCHK(c, ensure(&c->d_fdata, &c->fdata_cap, need));
+  uint8_t *data[5];
+  {
+    Timer t(c, "record_fields");
+    for (int f = 0; f < 5; f++) {
+      data[f] = (fields & col[f].bit) ? c->d_fdata + at[f] : nullptr;
+      if (!data[f]) continue;
+      const FieldGatherArgs ga{c->d_u, sa.roff, sa.bin_mq_nl, sa.flag_nc, sa.l_seq, off[col[f].off],
+                               n,      col[f].sh, col[f].bytes, data[f],
+                               reinterpret_cast<int64_t *>(c->d_fdata + tiles_at[f])};
+      HIPCHK(c, launch_field_gather(f, ga, c->stream));
+    }
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->fdev = sbam_record_fields{off[0], data[0], off[1], reinterpret_cast<uint32_t *>(data[1]), off[2], data[2],
+                               data[3], off[3], data[4]};
+  c->f_tot = tot;
+  c->f_i0 = i0;
+  c->f_n = n;
+  if (totals) *totals = tot;
+  return SBAM_OK;
+}
+
+int sbam_get_record_fields(sbam_ctx *c, const sbam_record_fields *o) {
+  if (!c || !o) return SBAM_ERR_ARG;
+  if (c->f_n < 0) return set_err(c, SBAM_ERR_STATE, "sbam_load_record_fields has not run");
+  if (c->f_n == 0) {  // an empty batch: each offset column is its single 0
+    for (int64_t *p : {o->name_off, o->cigar_off, o->seq_off, o->aux_off})
+      if (p) *p = 0;
+    return SBAM_OK;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const sbam_record_fields &d = c->fdev;
+  const size_t no = (size_t)(c->f_n + 1) * 8;
+  const struct { void *dst; const void *src; size_t bytes; bool offs; } cp[] = {
+      {o->name_off, d.name_off, no, true},   {o->name, d.name, (size_t)c->f_tot.name_bytes, false},
+      {o->cigar_off, d.cigar_off, no, true}, {o->cigar, d.cigar, (size_t)c->f_tot.cigar_ops * 4, false},
+      {o->seq_off, d.seq_off, no, true},     {o->seq, d.seq, (size_t)c->f_tot.seq_bases, false},
+      {o->qual, d.qual, (size_t)c->f_tot.seq_bases, false},
+      {o->aux_off, d.aux_off, no, true},     {o->aux, d.aux, (size_t)c->f_tot.aux_bytes, false}};
+  for (auto &e : cp)
+    if (e.dst && !e.src) return set_err(c, SBAM_ERR_ARG, "a requested field was not selected by sbam_load_record_fields");
+  for (auto &e : cp)
+    if (e.dst && e.bytes) HIPCHK(c, hipMemcpyAsync(e.dst, e.src, e.bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SBAM_OK;
+}
+
+int sbam_record_fields_device(sbam_ctx *c, sbam_record_fields *d, int64_t *i0, int64_t *n) {
+  if (!c || !d) return SBAM_ERR_ARG;
+  if (c->f_n < 0) return set_err(c, SBAM_ERR_STATE, "sbam_load_record_fields has not run");
+  *d = c->fdev;
+  if (i0) *i0 = c->f_i0;
+  if (n) *n = c->f_n;
   return SBAM_OK;
 }
 

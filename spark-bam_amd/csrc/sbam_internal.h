@@ -169,5 +169,36 @@ hipError_t launch_record_spans(const uint8_t *u, int64_t L, const int64_t *offs,
 hipError_t launch_record_columns(const uint8_t *u, const int64_t *offs, int64_t n, const int64_t *bstart,
                                  const int64_t *buoff, const int32_t *busize, int64_t nblocks, int64_t file_base,
                                  RecordColumnsDev cols, hipStream_t s);
+// Variable-length fields of decoded records as CSR columns (sbam_fields.hip).  All pointers address the batch's
+// first record; L is the stream's length.
+struct FieldSizesArgs {
+  const int64_t *roff;
+  const int32_t *block_size;
+  const uint32_t *bin_mq_nl, *flag_nc;
+  const int32_t *l_seq;
+  int64_t n, L;
+};
+struct FieldOffsets {  // n + 1 int64 each
+  int64_t *name, *cigar, *seq, *aux;
+};
+struct FieldGatherArgs {
+  const uint8_t *u;
+  const int64_t *roff;
+  const uint32_t *bin_mq_nl, *flag_nc;
+  const int32_t *l_seq;
+  const int64_t *off;  // the column's offsets, in units of 1 << sh bytes
+  int64_t n;
+  int32_t sh;
+  int64_t total;       // output bytes
+  uint8_t *out;        // 8-byte aligned, room for total rounded up to 8
+  int64_t *tiles;      // scratch: 2 * field_gather_tiles(total) int64 (each tile's first and last record)
+};
+int64_t field_size_blocks(int64_t n);  // entries per length of launch_field_sizes' bsum scratch
+int64_t field_gather_tiles(int64_t total);
+// lengths, validation (first_bad = min failing record index of the batch, ~0 when none) and offsets; totals[4]
+hipError_t launch_field_sizes(const FieldSizesArgs &a, int64_t *bsum, FieldOffsets off, unsigned long long *first_bad,
+                              int64_t *totals, hipStream_t s);
+// field: 0 name, 1 cigar, 2 seq (ASCII bases), 3 qual, 4 aux
+hipError_t launch_field_gather(int field, const FieldGatherArgs &a, hipStream_t s);
 
 }  // namespace sbam

@@ -28,6 +28,7 @@ LIB_PATH = os.environ.get("SBAM_LIB", os.path.join(_HERE, "..", "build", "libsba
 SBAM_OK = 0
 ERR_HEADER_PARSE, ERR_HEADER_SEARCH, ERR_INFLATE, ERR_NO_READ_FOUND, ERR_NOT_BAM, ERR_ARG, ERR_HIP, ERR_STATE, \
     ERR_HALO = range(1, 10)
+ERR_RECORD = 10
 
 FLAG_NAMES = [  # check/src/main/scala/org/hammerlab/bam/check/full/error/Flags.scala:201-223
     "tooFewFixedBlockBytes", "negativeReadIdx", "tooLargeReadIdx", "negativeReadPos", "tooLargeReadPos",
@@ -81,8 +82,13 @@ class HaloException(SbamError):
     code = ERR_HALO
 
 
+class RecordFieldsException(SbamError):
+    """A record whose variable-length fields overrun its block_size (sbam_load_record_fields)."""
+    code = ERR_RECORD
+
+
 _EXC = {c.code: c for c in (HeaderParseException, HeaderSearchFailedException, InflateException,
-                            NoReadFoundException, HaloException)}
+                            NoReadFoundException, HaloException, RecordFieldsException)}
 
 
 class _Pos(ctypes.Structure):
@@ -121,12 +127,47 @@ RECORD_COLUMNS = {"offset": np.int64, "block_pos": np.int64, "block_off": np.int
                   "l_seq": np.int32, "next_ref_id": np.int32, "next_pos": np.int32, "tlen": np.int32}
 
 
+class _RecordFields(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("name_off", "name", "cigar_off", "cigar", "seq_off", "seq", "qual",
+                                               "aux_off", "aux")]
+
+
+class _RecordFieldTotals(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ("name_bytes", "cigar_ops", "seq_bases", "aux_bytes")]
+
+
+# sbam_load_record_fields' mask bits, the data column's dtype, its offsets column and its total
+FIELD_BITS = {"name": 1, "cigar": 2, "seq": 4, "qual": 8, "aux": 16}
+_FIELD_LAYOUT = {"name": (np.uint8, "name_off", "name_bytes"), "cigar": (np.uint32, "cigar_off", "cigar_ops"),
+                 "seq": (np.uint8, "seq_off", "seq_bases"), "qual": (np.uint8, "seq_off", "seq_bases"),
+                 "aux": (np.uint8, "aux_off", "aux_bytes")}
+
+
+@dataclass
+class RecordFields:
+    """CSR columns of records [i0, i0 + n) (sbam_load_record_fields): `*_off` are int64[n + 1]; a data column that
+    was not selected (or everything, with host=False) is None."""
+    i0: int
+    n: int
+    totals: dict
+    name_off: Optional[np.ndarray] = None
+    name: Optional[np.ndarray] = None
+    cigar_off: Optional[np.ndarray] = None
+    cigar: Optional[np.ndarray] = None
+    seq_off: Optional[np.ndarray] = None
+    seq: Optional[np.ndarray] = None
+    qual: Optional[np.ndarray] = None
+    aux_off: Optional[np.ndarray] = None
+    aux: Optional[np.ndarray] = None
+
+
 EXPORTS = [  # every symbol include/sbam.h declares
     "sbam_open", "sbam_close", "sbam_load", "sbam_reserve", "sbam_last_error", "sbam_set_path", "sbam_reset", "sbam_version", "sbam_find_block_starts", "sbam_scan_blocks",
     "sbam_get_blocks", "sbam_inflate", "sbam_inflate_fallbacks", "sbam_read_uncompressed", "sbam_pos_to_offset", "sbam_offset_to_pos",
     "sbam_header", "sbam_set_contig_lengths", "sbam_check_eager", "sbam_check_full_words", "sbam_check_full_counts",
     "sbam_find_record_start", "sbam_file_splits", "sbam_split_records", "sbam_compute_splits",
     "sbam_record_offsets", "sbam_record_spans", "sbam_load_records", "sbam_get_record_columns", "sbam_record_columns_device",
+    "sbam_load_record_fields", "sbam_get_record_fields", "sbam_record_fields_device",
     "sbam_last_kernel_ms",
 ]
 
@@ -186,6 +227,9 @@ def load_library(path: str = LIB_PATH):
         "sbam_load_records": (ctypes.c_int, [vp, P(_SplitArgs), i64, i64, vp, P(i64)]),
         "sbam_get_record_columns": (ctypes.c_int, [vp, i64, i64, P(_RecordColumns)]),
         "sbam_record_columns_device": (ctypes.c_int, [vp, P(_RecordColumns), P(i64)]),
+        "sbam_load_record_fields": (ctypes.c_int, [vp, i64, i64, ctypes.c_uint32, P(_RecordFieldTotals)]),
+        "sbam_get_record_fields": (ctypes.c_int, [vp, P(_RecordFields)]),
+        "sbam_record_fields_device": (ctypes.c_int, [vp, P(_RecordFields), P(i64), P(i64)]),
         "sbam_last_kernel_ms": (ctypes.c_double, [vp, ctypes.c_char_p]),
     }
     for name, (res, args) in sig.items():
@@ -576,12 +620,47 @@ class BamFile:
         a = self._args(split_size, bgzf_blocks_to_check, reads_to_check, max_read_size, use_success_bitmap)
         self._check(self.L.sbam_load_records(self.ctx, ctypes.byref(a), first, count, _ptr(sizes), ctypes.byref(n)))
         sizes = sizes[:count]
+        self.n_loaded = int(n.value)
         if columns is None:
             return sizes, {}
         cols = {k: np.zeros(n.value, RECORD_COLUMNS[k]) for k in columns}
         rc = _RecordColumns(**{k: v.ctypes.data for k, v in cols.items()})
         self._check(self.L.sbam_get_record_columns(self.ctx, 0, n.value, ctypes.byref(rc)))
         return sizes, cols
+
+    def load_record_fields(self, i0: int = 0, n: Optional[int] = None,
+                           fields: Sequence[str] = ("name", "cigar", "seq", "qual", "aux"), host: bool = True):
+        """Names, CIGARs, bases, qualities and tags of records [i0, i0 + n) of the last load_records, decoded on the
+        GPU into CSR columns (sbam_load_record_fields: what htsjdk's BAMRecordCodec.decode gives loadReads' SAMRecords,
+        CanLoadBam.scala:221-241).  `n=None`: through the last loaded record.  Returns a RecordFields with the numpy
+        columns; with host=False it holds only the totals and the columns stay on the device
+        (sbam_record_fields_device)."""
+        if n is None:
+            n = max(getattr(self, "n_loaded", 0) - i0, 0)
+        mask = 0
+        for f in fields:
+            if f not in FIELD_BITS:
+                raise ValueError(f"unknown field {f!r}")
+            mask |= FIELD_BITS[f]
+        tot = _RecordFieldTotals()
+        self._check(self.L.sbam_load_record_fields(self.ctx, int(i0), int(n), mask, ctypes.byref(tot)))
+        totals = {k: int(getattr(tot, k)) for k, _ in _RecordFieldTotals._fields_}
+        out = RecordFields(int(i0), int(n), totals)
+        if not host:
+            return out
+        ptrs = {}
+        for name in ("name_off", "cigar_off", "seq_off", "aux_off"):
+            a = np.zeros(n + 1, np.int64)
+            setattr(out, name, a)
+            ptrs[name] = a.ctypes.data
+        for f in fields:
+            dt, _, tk = _FIELD_LAYOUT[f]
+            a = np.zeros(totals[tk], dt)
+            setattr(out, f, a)
+            ptrs[f] = a.ctypes.data if a.size else None
+        rf = _RecordFields(**ptrs)
+        self._check(self.L.sbam_get_record_fields(self.ctx, ctypes.byref(rf)))
+        return out
 
     def record_spans(self, offsets: np.ndarray):
         """(ref_id, start, end) of the records at `offsets`: [getStart - 1, getEnd) as CanLoadBam.region uses it

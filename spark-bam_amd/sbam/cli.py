@@ -8,6 +8,7 @@
     python -m sbam.cli index-records BAM [OUT]
     python -m sbam.cli compute-splits [-s] [-l LIMIT] [-m SPLIT] BAM [OUT]
     python -m sbam.cli count-reads [-m SPLIT] BAM [OUT]
+    python -m sbam.cli view [-h] [-m SPLIT] BAM [OUT]
 
 Report text follows the reference apps line for line, so the goldens of cli/src/test/resources/output/ diff
 verbatim (tests/test_cli.py):
@@ -19,7 +20,9 @@ verbatim (tests/test_cli.py):
   * index-blocks / index-records: bgzf/.../index/IndexBlocks.scala, check/.../bam/index/IndexRecords.scala (the
     `.blocks` / `.records` sidecars);
   * compute-splits: ComputeSplits.scala:56-68 (-s: spark-bam splits only; hadoop-bam comparison is out of scope);
-  * count-reads: compare/CountReads.scala:80-100, spark-bam side only.
+  * count-reads: compare/CountReads.scala:80-100, spark-bam side only;
+  * view: the records of loadReads (CanLoadBam.scala:348-352) as SAM text (sbam.sam; pinned by the reference's 2.sam
+    and 5k.sam), decoded on the GPU by sbam_load_record_fields.
 Counting, checking and splitting all run through libsbam.so (sbam.BamFile); this module only formats."""
 from __future__ import annotations
 
@@ -642,9 +645,56 @@ def index_records_lines(f: sbam.BamFile) -> List[str]:
     return [str(f.pos_of(x)).replace(":", ",") for x in offs]
 
 
+# ---- view ----------------------------------------------------------------------------------------------------
+VIEW_BATCH = 1 << 20  # records decoded per sbam_load_record_fields call
+
+
+def header_text(f: sbam.BamFile) -> str:
+    """The BAM header's SAM text as stored (Header.scala:26-60: magic, l_text, text)."""
+    lt = int.from_bytes(f.read_uncompressed(4, 4), "little")
+    return f.read_uncompressed(8, lt).rstrip(b"\0").decode("latin-1")
+
+
+def view_lines(f: sbam.BamFile, split_size: int, batch: int = VIEW_BATCH):
+    """SAM lines of the records of all partitions in order (loadReads, CanLoadBam.scala:348-352, printed as htsjdk
+    prints SAMRecords): records from sbam_load_records, names / CIGARs / bases / qualities / tags from
+    sbam_load_record_fields in batches of at most `batch` records, text from sbam.sam."""
+    from sbam import sam
+    names = header_names(f)
+    _, cols = f.load_records(split_size, columns=("ref_id", "pos", "bin_mq_nl", "flag_nc", "next_ref_id", "next_pos",
+                                                  "tlen"))
+    n = f.n_loaded
+    for i0 in range(0, n, batch):
+        k = min(batch, n - i0)
+        rf = f.load_record_fields(i0, k)
+        yield from sam.sam_lines({c: v[i0:i0 + k] for c, v in cols.items()}, rf, names)
+
+
+def view_main(a) -> int:
+    data = open(a.bam, "rb").read()
+    out = open(a.out, "wb") if a.out else sys.stdout.buffer  # bytes as stored (names and tags are not re-encoded)
+    try:
+        with sbam.BamFile(data, path=a.bam) as f:
+            if a.header:
+                text = header_text(f)
+                out.write((text if not text or text.endswith("\n") else text + "\n").encode("latin-1"))
+            for ln in view_lines(f, sbam.effective_split_size(a.max_split_size)):
+                out.write(ln.encode("latin-1") + b"\n")
+    finally:
+        if a.out:
+            out.close()
+    return 0
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
     ap = argparse.ArgumentParser(prog="sbam.cli")
     sub = ap.add_subparsers(dest="cmd", required=True)
+    p = sub.add_parser("view", add_help=False)  # (-h is samtools view's "with header", not help)
+    p.add_argument("--help", action="help")
+    p.add_argument("-h", "--header", action="store_true", help="print the BAM header text first")
+    p.add_argument("-m", "--max-split-size", type=parse_bytes, default=None)
+    p.add_argument("bam")
+    p.add_argument("out", nargs="?")
     for name in ("full-check", "check-bam", "check-blocks", "compute-splits", "count-reads", "index-blocks",
                  "index-records"):
         p = sub.add_parser(name)
@@ -668,6 +718,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             p.add_argument("--dist-backend", default="nccl", help="nccl (RCCL); gloo to rehearse ranks on one GPU")
             p.add_argument("--device", type=int, default=None, help="GPU of every rank (default LOCAL_RANK)")
     a = ap.parse_args(argv)
+    if a.cmd == "view":
+        return view_main(a)
     if getattr(a, "gpus", 1) > 1:
         if "WORLD_SIZE" not in os.environ:
             return spawn_ranks(a.gpus, sys.argv[1:] if argv is None else argv)
