@@ -2,7 +2,8 @@
 //
 // Semantics: java.util.zip.Inflater(nowrap).inflate(decBuf, 0, ISIZE) on the block payload, as the reference
 // calls it (bgzf/src/main/scala/org/hammerlab/bgzf/block/Stream.scala:31-71), i.e. zlib inflate():
-//   * output stops at ISIZE (remaining input is ignored); ISIZE 0 returns 0 at once;
+//   * output stops at ISIZE; the input after byte ISIZE is still decoded up to the first symbol that needs room (an
+//     invalid symbol or block header there is a DATA error with ISIZE bytes found); ISIZE 0 returns 0 at once;
 //   * the stream ending (final EOB, or input exhausted mid-symbol) before ISIZE bytes → "found" count (SHORT);
 //   * invalid streams (bad block type, stored LEN/NLEN, over-subscribed / incomplete codes, missing EOB code,
 //     bad repeat, invalid symbols, distance too far back) → DATA error; CRC32 is never checked.
@@ -303,6 +304,12 @@ __global__ __launch_bounds__(kDecThreads, 2) void k_inflate_slow(const uint8_t *
   TokOut to{0, 0, 0, 0, 0, 0, 0, 0, 0, false, 0};
   Canon lc, dc;
   int32_t o = 0, us = 0, err = INF_OK, sleft = 0, fin = 0;
+  // zlib looks for room only when a symbol has output to write: once byte ISIZE is out (by a literal, a match or a
+  // stored block that ends exactly there) it decodes on, through end-of-block symbols and block headers, until a
+  // literal, a complete length / distance pair or stored data needs room, the stream or the input ends (all fine:
+  // inflate returns ISIZE bytes), or it meets an invalid header or symbol, which is a data error with ISIZE bytes
+  // found.  drain = decoding on with the output full.
+  bool drain = false;
   auto refill = [&]() {  // the symbol loop's refill: next dword from the register window
     if (br.bc <= 32) {
       br.bb |= (uint64_t)br.nx << br.bc;
@@ -325,6 +332,7 @@ __global__ __launch_bounds__(kDecThreads, 2) void k_inflate_slow(const uint8_t *
         o = 0;
         fin = 0;
         err = INF_OK;
+        drain = false;
         const int32_t dlen = cs - hs - 8;  // Stream.scala: dataLength = compressedSize - headerSize - FOOTER_SIZE
         if (us == 0) {
           state = S_DONE;  // inflate(buf, 0, 0) returns 0
@@ -592,12 +600,17 @@ __global__ __launch_bounds__(kDecThreads, 2) void k_inflate_slow(const uint8_t *
         int len = 0;
         bool is_len = false;
         if (sym < 256) {
-          if (!tok_put(to, (uint32_t)sym, pool)) err = INF_OVERFLOW;
-          o++;
-          if (o == us || err != INF_OK) state = S_DONE;
+          if (drain) {
+            state = S_DONE;  // no room for it: inflate returns
+          } else {
+            if (!tok_put(to, (uint32_t)sym, pool)) err = INF_OVERFLOW;
+            o++;
+            if (err != INF_OK) state = S_DONE;
+            else drain = o == us;
+          }
         } else if (sym == 256) {
           if (fin) {
-            err = INF_SHORT;  // stream end before ISIZE bytes
+            err = drain ? INF_OK : INF_SHORT;  // stream end before ISIZE bytes
             state = S_DONE;
           } else {
             state = S_PARK;
@@ -617,7 +630,7 @@ __global__ __launch_bounds__(kDecThreads, 2) void k_inflate_slow(const uint8_t *
         }
         // second slot: the distance after a length, or a second literal after a literal (taken only when it
         // is a complete, valid literal; anything else is left for the next step, which decodes it afresh)
-        if (is_len || (sym < 256 && state == S_HUFF)) {
+        if (is_len || (sym < 256 && state == S_HUFF && !drain)) {
           refill();
           int L2, h2;
           bool v2;
@@ -628,7 +641,8 @@ __global__ __launch_bounds__(kDecThreads, 2) void k_inflate_slow(const uint8_t *
               br.drop(L2);
               if (!tok_put(to, (uint32_t)b2, pool)) err = INF_OVERFLOW;
               o++;
-              if (o == us || err != INF_OK) state = S_DONE;
+              if (err != INF_OK) state = S_DONE;
+              else drain = o == us;
             }
           } else {
             const int ds = b2;
@@ -648,7 +662,9 @@ __global__ __launch_bounds__(kDecThreads, 2) void k_inflate_slow(const uint8_t *
               } else {
                 const int dist = db + (int)br.peek(dx);
                 br.drop(dx);
-                if (dist > o) {
+                if (drain) {
+                  state = S_DONE;  // a complete pair and no room (zlib tests the distance only when it copies)
+                } else if (dist > o) {
                   err = INF_DATA;  // invalid distance too far back
                   state = S_DONE;
                 } else {
@@ -656,8 +672,10 @@ __global__ __launch_bounds__(kDecThreads, 2) void k_inflate_slow(const uint8_t *
                   ok = ok && tok_put(to, (uint32_t)(len + 253), pool);
                   ok = ok && tok_put(to, kTokDist | (uint32_t)(dist - 1), pool);
                   if (!ok) err = INF_OVERFLOW;
+                  // (a match cut short by ISIZE is still pending when inflate returns; one ending there is not)
+                  if (o + len > us || err != INF_OK) state = S_DONE;
+                  else drain = o + len == us;
                   o = min(o + len, us);
-                  if (o == us || err != INF_OK) state = S_DONE;
                 }
               }
             }
@@ -667,7 +685,8 @@ __global__ __launch_bounds__(kDecThreads, 2) void k_inflate_slow(const uint8_t *
     } else if (state == S_STORED) {
       // --- up to 2 stored bytes per step (byte-aligned: bb's low bits are the next byte)
       refill();
-      const int n = min(min(sleft, 2), us - o);
+      if (drain && sleft > 0) state = S_DONE;  // stored data and no room
+      const int n = state == S_DONE ? 0 : min(min(sleft, 2), us - o);
       int m = 0;
       for (int i = 0; i < 2; i++) {
         if (i < n && br.left >= 8 && err == INF_OK) {
@@ -678,15 +697,16 @@ __global__ __launch_bounds__(kDecThreads, 2) void k_inflate_slow(const uint8_t *
       }
       o += m;
       sleft -= m;
-      if (err != INF_OK) state = S_DONE;
+      if (err != INF_OK || state == S_DONE) state = S_DONE;
       else if (m < n) {
         err = INF_SHORT;
         state = S_DONE;
-      } else if (o == us) {
+      } else if (o == us && sleft > 0) {
         state = S_DONE;
       } else if (sleft == 0) {
+        drain = o == us;
         if (fin) {
-          err = INF_SHORT;
+          err = drain ? INF_OK : INF_SHORT;
           state = S_DONE;
         } else {
           state = S_PARK;
@@ -694,6 +714,8 @@ __global__ __launch_bounds__(kDecThreads, 2) void k_inflate_slow(const uint8_t *
       }
     }
     if (state == S_DONE) {
+      if (drain && err == INF_SHORT) err = INF_OK;  // the input ended with the output full: inflate returns ISIZE bytes
+      drain = false;
       if (err != INF_OVERFLOW) {  // final (padded) chunk and any pending one leave now
         bool ok = true;
         if (to.n > 0)
