@@ -18,96 +18,234 @@
 
 using namespace sbam;
 
+namespace {
+
+#define HIPTRY(expr)                 \
+  do {                               \
+    hipError_t e_ = (expr);          \
+    if (e_ != hipSuccess) return e_; \
+  } while (0)
+
+// SBAM_LOG_GROW=1: report every reallocation of an existing buffer (the streamed pipe's stalls)
+bool log_grow() {
+  static const bool on = [] {
+    const char *e = std::getenv("SBAM_LOG_GROW");
+    return e && *e && *e != '0';
+  }();
+  return on;
+}
+
+// Owned, grow-only device buffer: reused across sbam_reset() so a re-run allocates nothing; frees itself (with the
+// owner's device current: sbam_close, or the entry point a local one lives in).
+template <class T>
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() {
+    if (p_) (void)hipFree(p_);
+  }
+  // Room for n elements (at least one).  An allocation that is large enough is kept; else a new one replaces it and
+  // the contents are lost: *grew is then set (a buffer never allocated held no stage's data, and sets nothing).
+  hipError_t ensure(size_t n, bool *grew = nullptr) {
+    if (p_ && size_ >= n) return hipSuccess;
+    const size_t m = std::max<size_t>(n, 1);
+    if (p_ && log_grow()) std::fprintf(stderr, "[sbam] grow %zu -> %zu bytes\n", size_ * sizeof(T), m * sizeof(T));
+    if (p_ && grew) *grew = true;
+    if (p_) (void)hipFree(p_);  // (first: the two need not fit side by side)
+    size_ = 0;
+    const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p_), m * sizeof(T));
+    if (e == hipSuccess) size_ = m;
+    else p_ = nullptr;
+    return e;
+  }
+  void swap(DevBuf &o) {
+    std::swap(p_, o.p_);
+    std::swap(size_, o.size_);
+  }
+  size_t size() const { return size_; }  // elements allocated
+  T *get() const { return p_; }
+  operator T *() const { return p_; }
+
+ private:
+  T *p_ = nullptr;
+  size_t size_ = 0;
+};
+
+// Token arena (TokPool): blocks whose tokens outgrow their main region.  The allocation has 1 KiB more than the
+// usable bytes: the resolver's token lookahead.
+struct TokArena {
+  DevBuf<uint8_t> buf;
+  size_t usable() const { return buf.size() ? buf.size() - 1024 : 0; }
+  hipError_t ensure(size_t bytes, bool *grew = nullptr) { return buf.ensure(bytes + 1024, grew); }
+};
+
+// Host mirror of the scanned block table (relative offsets).  The fast scan's table comes back behind the GPU, into
+// pinned staging: the stream's length on the main stream (ev[0]), the columns on copy_stream, beside the decoder,
+// once the table is built (ev[2]; ev[1] when they have landed).  get() moves them into the vectors when the host
+// first reads them (sbam_inflate: while the decoder runs); total() needs only the length.
+struct BlockMirror {
+  int64_t n = -1;  // blocks of the scanned table; -1: sbam_scan_blocks has not run
+  std::vector<int64_t> start, uoff;  // (uoff: n + 1 entries, the last one the stream's length)
+  std::vector<int32_t> csize, usize;
+  uint8_t *stage = nullptr;  // pinned: length | start[n] | uoff[n + 1] | csize[n] | usize[n]
+  size_t stage_bytes = 0;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  hipStream_t copy_stream = nullptr;
+  bool pending = false;  // the table is in staging (or on its way there), not yet in the vectors
+
+  // No table.  Waits for a column copy nobody read: it reads the device columns and writes the staging that the
+  // next table reuses, and must not land over that table later.
+  hipError_t invalidate() {
+    const hipError_t e = pending ? hipEventSynchronize(ev[1]) : hipSuccess;
+    pending = false;
+    n = -1;  // (the vectors keep their storage; fill() and get() replace their contents)
+    return e;
+  }
+  // After a fast scan: queue the host's copy of the nb-block device table behind the work on s; not waited for.
+  hipError_t start_copy(const int64_t *d_start, const int64_t *d_uoff, const int32_t *d_csize, const int32_t *d_usize,
+                        int64_t nb, hipStream_t s) {
+    const size_t need = 8 + (size_t)nb * 8 + (size_t)(nb + 1) * 8 + (size_t)nb * 8;
+    if (stage_bytes < need) {
+      HIPTRY(hipStreamSynchronize(s));  // (an earlier table's length copy may still target the old staging)
+      if (stage) (void)hipHostFree(stage);
+      stage = nullptr;
+      stage_bytes = 0;
+      HIPTRY(hipHostMalloc(reinterpret_cast<void **>(&stage), need + need / 8, hipHostMallocDefault));
+      stage_bytes = need + need / 8;
+    }
+    for (hipEvent_t &e : ev)
+      if (!e) HIPTRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (!copy_stream) HIPTRY(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
+    int64_t *st = reinterpret_cast<int64_t *>(stage + 8), *uo = st + nb;
+    int32_t *cs = reinterpret_cast<int32_t *>(uo + nb + 1), *us = cs + nb;
+    HIPTRY(hipMemcpyAsync(stage, d_uoff + nb, 8, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipEventRecord(ev[0], s));
+    HIPTRY(hipEventRecord(ev[2], s));
+    HIPTRY(hipStreamWaitEvent(copy_stream, ev[2], 0));
+    HIPTRY(hipMemcpyAsync(uo, d_uoff, (nb + 1) * 8, hipMemcpyDeviceToHost, copy_stream));
+    if (nb) {
+      HIPTRY(hipMemcpyAsync(st, d_start, nb * 8, hipMemcpyDeviceToHost, copy_stream));
+      HIPTRY(hipMemcpyAsync(cs, d_csize, nb * 4, hipMemcpyDeviceToHost, copy_stream));
+      HIPTRY(hipMemcpyAsync(us, d_usize, nb * 4, hipMemcpyDeviceToHost, copy_stream));
+    }
+    HIPTRY(hipEventRecord(ev[1], copy_stream));
+    n = nb;
+    pending = true;
+    return hipSuccess;
+  }
+  // After the host walk: the table it built (uoff follows from usize).
+  void fill(std::vector<int64_t> &&st, std::vector<int32_t> &&cs, std::vector<int32_t> &&us) {
+    start = std::move(st);
+    csize = std::move(cs);
+    usize = std::move(us);
+    n = (int64_t)start.size();
+    uoff.resize(n + 1);
+    int64_t acc = 0;
+    for (int64_t b = 0; b < n; b++) {
+      uoff[b] = acc;
+      acc += (usize[b] < 0) ? 0 : usize[b];
+    }
+    uoff[n] = acc;
+    pending = false;
+  }
+  // the scanned stream's uncompressed length (waits only for its own 8-byte copy)
+  hipError_t total(int64_t *L) {
+    if (pending) {
+      HIPTRY(hipEventSynchronize(ev[0]));
+      *L = *reinterpret_cast<const int64_t *>(stage);
+    } else {
+      *L = uoff[n];
+    }
+    return hipSuccess;
+  }
+  // the vectors, valid: waits for the columns and unpacks the staging once
+  hipError_t get() {
+    if (!pending) return hipSuccess;
+    HIPTRY(hipEventSynchronize(ev[1]));
+    const int64_t *st = reinterpret_cast<const int64_t *>(stage + 8), *uo = st + n;
+    const int32_t *cs = reinterpret_cast<const int32_t *>(uo + n + 1), *us = cs + n;
+    start.assign(st, st + n);
+    uoff.assign(uo, uo + n + 1);
+    csize.assign(cs, cs + n);
+    usize.assign(us, us + n);
+    pending = false;
+    return hipSuccess;
+  }
+  // (sbam_close, both streams idle)
+  void destroy() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (copy_stream) (void)hipStreamDestroy(copy_stream);
+    if (stage) (void)hipHostFree(stage);
+  }
+};
+
+}  // namespace
+
 struct sbam_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   int64_t D = 0, base = 0, file_size = 0;
-  uint8_t *d_comp = nullptr;
-  size_t comp_cap = 0;
-  // list-form chain pass scratch (launch_chain_list_*)
-  int32_t *d_ccnt = nullptr;
-  int32_t *d_tcnt = nullptr;  // record-0 pass: PASS0 positions per tile and wave (CountsDev::tile_pass0)
-  size_t tcnt_cap = 0;
-  int64_t *d_coff2 = nullptr, *d_plist = nullptr, *d_pfb = nullptr;
-  uint8_t *d_pok = nullptr;
-  unsigned long long *d_nfb = nullptr;
-  size_t ccnt_cap = 0, coff2_cap = 0, plist_cap = 0, pfb_cap = 0, pok_cap = 0, nfb_cap = 0;
+  DevBuf<uint8_t> d_comp;
   // candidates from the header scan
-  Candidate *d_cand = nullptr;
+  DevBuf<Candidate> d_cand;
   int64_t ncand = -1;
-  size_t cand_cap = 0;
-  int32_t *d_cc = nullptr;
-  int64_t *d_coff = nullptr;
-  size_t cc_cap = 0, coff_cap = 0;
-  Candidate *d_slots = nullptr;  // one-pass scan: kScanSlots per chunk
-  size_t slots_cap = 0;
+  DevBuf<int32_t> d_cc;
+  DevBuf<int64_t> d_coff;
+  DevBuf<Candidate> d_slots;  // one-pass scan: kScanSlots per chunk
   // per-call query scratch (split starts / answers): kept, since hipMalloc + hipFree per call cost ~0.5 ms of
   // host time each (a device-wide synchronisation) between the kernels of a step
-  int64_t *d_qa = nullptr, *d_qb = nullptr;
-  size_t qa_cap = 0, qb_cap = 0, lens_cap = 0;
-  // block table (relative offsets), device + host
-  int64_t nblocks = -1;
-  int64_t *d_bstart = nullptr, *d_buoff = nullptr;
-  int32_t *d_bh = nullptr, *d_bc = nullptr, *d_bu = nullptr;
-  size_t bcap[5] = {0, 0, 0, 0, 0};
-  std::vector<int64_t> h_bstart, h_buoff;
-  std::vector<int32_t> h_bc, h_bu;
-  // the fast scan's table comes back behind the GPU, into pinned staging (the stream's length first, then the
-  // columns); host_blocks() moves it into h_* when the host first reads them (sbam_inflate: while the decoder runs)
-  uint8_t *h_stage = nullptr;
-  size_t stage_cap = 0;
-  hipEvent_t blk_ev[3] = {nullptr, nullptr, nullptr};  // [0]: the length copied, [1]: the columns copied, [2]: built
-  hipStream_t copy_stream = nullptr;  // the columns' copy runs here, beside the decoder
-  bool blk_pending = false;
+  DevBuf<int64_t> d_qa, d_qb;
+  // block table (relative offsets): device columns, and the host mirror that owns the scan's state (blk.n)
+  DevBuf<int64_t> d_bstart, d_buoff;
+  DevBuf<int32_t> d_bh, d_bc, d_bu;
+  BlockMirror blk;
   // uncompressed stream
-  uint8_t *d_u = nullptr;
-  size_t u_cap = 0;
+  DevBuf<uint8_t> d_u;
   int64_t L = -1;
-  int32_t *d_status = nullptr, *d_found = nullptr;
-  size_t status_cap = 0, found_cap = 0;
+  DevBuf<int32_t> d_status, d_found;
+  // inflate scratch: token pages of the decode → resolve path
+  DevBuf<uint8_t> d_pool;  // main token regions (inflate_token_bytes)
+  TokArena arena;
+  DevBuf<int64_t> d_tokbase;
+  DevBuf<int32_t> d_slow;        // blocks the wave decoder hands to the exact per-lane decoder
+  DevBuf<unsigned int> d_icnt;   // slow-path blocks, slow-path work, resolve work, stored-only blocks
+  int64_t inflate_slow = -1;     // blocks the last sbam_inflate decoded on the exact per-lane path
   // contig lengths
   int32_t nref = -1;
-  int64_t *d_lens = nullptr;
+  DevBuf<int64_t> d_lens;
   std::vector<int64_t> h_lens;
   sbam_pos header_end{0, 0, 0};
-  // success bitmap of the latest full/eager check
-  unsigned long long *d_bitmap = nullptr;
-  size_t bitmap_cap = 0;
+  // success bitmap of the latest full/eager check, and what it covers (set_bitmap / drop_bitmap)
+  DevBuf<unsigned long long> d_bitmap;
   int64_t bm_x0 = 0, bm_x1 = 0;
+  int32_t bm_R = -1;
   bool bm_valid = false;
   bool bm_list = false;  // the bitmap came from the list-form chain pass: d_nfb[1..2] describe its links
   int64_t plist_n = 0;   // (and d_plist[0, plist_n) its PASS0 positions)
-  int32_t bm_R = -1;
-  // inflate scratch: token pages of the decode → resolve path
-  uint8_t *d_pool = nullptr;  // main token regions (inflate_token_bytes)
-  size_t pool_cap = 0;
-  uint8_t *d_arena = nullptr;  // token arena (TokPool): blocks whose tokens outgrow their main region
-  size_t arena_cap = 0;        // bytes (the allocation has 1 KiB more: the resolver's token lookahead)
-  int64_t *d_tokbase = nullptr;
-  size_t tokbase_cap = 0;
-  int32_t *d_slow = nullptr;  // blocks the wave decoder hands to the exact per-lane decoder
-  size_t slow_cap = 0;
-  unsigned int *d_icnt = nullptr;  // slow-path blocks, slow-path work, resolve work, stored-only blocks
-  int64_t inflate_slow = -1;       // blocks the last sbam_inflate decoded on the exact per-lane path
-  // split chains: per-split first record / chain end / count / record base (grow-only)
-  int64_t *d_sx = nullptr, *d_se = nullptr, *d_sn = nullptr, *d_sb = nullptr;
-  size_t sx_cap = 0, se_cap = 0, sn_cap = 0, sb_cap = 0;
+  // list-form chain pass scratch (launch_chain_list_*)
+  DevBuf<int32_t> d_ccnt;
+  DevBuf<int32_t> d_tcnt;  // record-0 pass: PASS0 positions per tile and wave (CountsDev::tile_pass0)
+  DevBuf<int64_t> d_coff2, d_plist, d_pfb;
+  DevBuf<uint8_t> d_pok;
+  DevBuf<unsigned long long> d_nfb;
+  // split chains: per-split first record / chain end / count / record base
+  DevBuf<int64_t> d_sx, d_se, d_sn, d_sb;
   // decoded records of the last sbam_load_records (offset column + RecordColumnsDev in one arena)
-  int64_t *d_roff = nullptr;
-  size_t roff_cap = 0;
-  uint8_t *d_rcols = nullptr;
-  size_t rcols_cap = 0;
+  DevBuf<int64_t> d_roff;
+  DevBuf<uint8_t> d_rcols;
   RecordColumnsDev rcols{};
   int64_t n_loaded = -1;
   // variable-length fields of the last sbam_load_record_fields: offsets + scan scratch, and the data arena
-  uint8_t *d_foff = nullptr, *d_fdata = nullptr;
-  size_t foff_cap = 0, fdata_cap = 0;
+  DevBuf<uint8_t> d_foff, d_fdata;
   sbam_record_fields fdev{};  // device pointers (data of unselected fields: null)
   int64_t f_i0 = 0, f_n = -1;
   sbam_record_field_totals f_tot{};
   // small device scratch
-  int64_t *d_small = nullptr;  // 64 int64
-  unsigned long long *d_counts = nullptr;
+  DevBuf<int64_t> d_small;  // 64 int64
+  DevBuf<unsigned long long> d_counts;
   // timing
   std::map<std::string, std::pair<hipEvent_t, hipEvent_t>> ev;
   // sbam_load's copy pieces in flight (hipEventDisableTiming events, created on first use)
@@ -135,36 +273,6 @@ int set_err(sbam_ctx *c, int code, const char *fmt, ...) {
     if (e_ != hipSuccess) return set_err(ctx, SBAM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
-template <class T>
-hipError_t dalloc(T **p, size_t n) {
-  return hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(n, 1) * sizeof(T));
-}
-template <class T>
-void dfree(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-// SBAM_LOG_GROW=1: report every reallocation of an existing buffer (the streamed pipe's stalls)
-bool log_grow() {
-  static const bool on = [] {
-    const char *e = std::getenv("SBAM_LOG_GROW");
-    return e && *e && *e != '0';
-  }();
-  return on;
-}
-// grow-only device buffer: reused across sbam_reset() so a re-run allocates nothing
-template <class T>
-hipError_t ensure(T **p, size_t *cap, size_t n) {
-  if (*p && *cap >= n) return hipSuccess;
-  if (*p && log_grow())
-    std::fprintf(stderr, "[sbam] grow %zu -> %zu bytes\n", *cap * sizeof(T), std::max<size_t>(n, 1) * sizeof(T));
-  dfree(*p);
-  *cap = 0;
-  hipError_t e = dalloc(p, n);
-  if (e == hipSuccess) *cap = std::max<size_t>(n, 1);
-  return e;
-}
-
 struct Timer {  // HIP events around a launch family on the ctx stream
   sbam_ctx *c;
   std::pair<hipEvent_t, hipEvent_t> *e;
@@ -184,6 +292,88 @@ struct Timer {  // HIP events around a launch family on the ctx stream
 
 StreamView view(sbam_ctx *c) {
   return StreamView{c->d_u, c->L, c->d_lens, c->nref, (c->base + c->D >= c->file_size) ? 1 : 0};
+}
+
+// ---- stage state -----------------------------------------------------------------------------------
+// What a check left in d_bitmap; dropped by whatever changes the stream or the checker's inputs under it.
+void set_bitmap(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, bool list_form) {
+  c->bm_x0 = x0 & ~(int64_t)63;
+  c->bm_x1 = x1;
+  c->bm_R = R;
+  c->bm_list = list_form;
+  c->bm_valid = true;
+}
+void drop_bitmap(sbam_ctx *c) { c->bm_valid = c->bm_list = false; }
+
+// The stages a context can hold: candidates, block table, stream (with its bitmap), records (with their fields).
+bool any_stage_ran(const sbam_ctx *c) { return c->ncand >= 0 || c->blk.n >= 0 || c->L >= 0 || c->n_loaded >= 0; }
+hipError_t drop_stages(sbam_ctx *c) {
+  c->ncand = -1;
+  const hipError_t e = c->blk.invalidate();
+  c->L = -1;
+  c->inflate_slow = -1;
+  drop_bitmap(c);
+  c->n_loaded = -1;
+  c->f_n = -1;
+  return e;
+}
+
+// ---- one size rule per stage ---------------------------------------------------------------------------
+// Each stage sizes its buffers here from its natural sizes, and sbam_reserve calls the same functions with its
+// estimates, so a reserved context's stages find every buffer large enough.  *grew: an existing buffer was replaced.
+int64_t scan_chunks(int64_t comp_bytes) { return (comp_bytes + kScanChunk - 1) / kScanChunk; }
+hipError_t ensure_scan(sbam_ctx *c, int64_t comp_bytes, bool *grew = nullptr) {
+  const int64_t nchunks = scan_chunks(comp_bytes);
+  HIPTRY(c->d_cc.ensure(nchunks, grew));
+  HIPTRY(c->d_coff.ensure(nchunks, grew));
+  return c->d_slots.ensure((size_t)nchunks * kScanSlots, grew);
+}
+hipError_t ensure_table(sbam_ctx *c, int64_t nb, bool *grew = nullptr) {
+  HIPTRY(c->d_bstart.ensure(nb + 1, grew));
+  HIPTRY(c->d_bh.ensure(nb + 1, grew));
+  HIPTRY(c->d_bc.ensure(nb + 1, grew));
+  HIPTRY(c->d_bu.ensure(nb + 1, grew));
+  return c->d_buoff.ensure(nb + 1 + (nb + 255) / 256, grew);  // (+ launch_gather_blocks' per-workgroup sums)
+}
+hipError_t ensure_inflate(sbam_ctx *c, int64_t L, int64_t nb, bool *grew = nullptr) {
+  HIPTRY(c->d_u.ensure((size_t)L + kStreamPad, grew));
+  HIPTRY(c->d_status.ensure(nb, grew));
+  HIPTRY(c->d_found.ensure(nb, grew));
+  // token pool (TokPool): main regions at 1 B per output byte, the arena for blocks that need more
+  HIPTRY(c->d_pool.ensure(inflate_token_bytes(L, nb), grew));
+  HIPTRY(c->arena.ensure(inflate_arena_bytes(L), grew));
+  HIPTRY(c->d_tokbase.ensure(nb, grew));
+  HIPTRY(c->d_slow.ensure(2 * nb, grew));  // (the exact decoder's list, then the stored-only list)
+  return c->d_icnt.ensure(4);
+}
+// bitmap words covering [x0 & ~63, x1)
+hipError_t ensure_bitmap(sbam_ctx *c, int64_t x0, int64_t x1, bool *grew = nullptr) {
+  return c->d_bitmap.ensure((size_t)((x1 - (x0 & ~(int64_t)63) + 63) / 64) + 1, grew);
+}
+// (the full check: the bitmap and the record-0 pass's per-tile counts; + 8: an unaligned x0 may add a tile)
+hipError_t ensure_check(sbam_ctx *c, int64_t x0, int64_t x1, bool *grew = nullptr) {
+  HIPTRY(ensure_bitmap(c, x0, x1, grew));
+  return c->d_tcnt.ensure((size_t)(4 * check_tiles(x0, x1) + 8), grew);
+}
+hipError_t ensure_chain_list(sbam_ctx *c, size_t n, bool *grew = nullptr) {
+  HIPTRY(c->d_plist.ensure(n, grew));
+  HIPTRY(c->d_pfb.ensure(n, grew));
+  HIPTRY(c->d_pok.ensure(n, grew));
+  return c->d_nfb.ensure(3);
+}
+// loadReads' N records: the offset column, and an int64 column and ten int32 ones (each 256-B aligned) in one
+// arena, carved into *cols
+hipError_t ensure_record_columns(sbam_ctx *c, size_t N, bool *grew = nullptr, RecordColumnsDev *cols = nullptr) {
+  HIPTRY(c->d_roff.ensure(N, grew));
+  const size_t stride = (std::max<size_t>(N, 1) * 8 + 255) & ~(size_t)255;
+  const size_t stride4 = (std::max<size_t>(N, 1) * 4 + 255) & ~(size_t)255;
+  HIPTRY(c->d_rcols.ensure(stride + 10 * stride4, grew));
+  if (!cols) return hipSuccess;
+  uint8_t *p = c->d_rcols;
+  auto q = [&](int j) { return reinterpret_cast<int32_t *>(p + stride + j * stride4); };
+  auto qu = [&](int j) { return reinterpret_cast<uint32_t *>(q(j)); };
+  *cols = RecordColumnsDev{reinterpret_cast<int64_t *>(p), q(0), q(1), q(2), q(3), qu(4), qu(5), q(6), q(7), q(8), q(9)};
+  return hipSuccess;
 }
 
 // Header.make details at relative offset q (for HeaderParseException).
@@ -213,81 +403,49 @@ int no_read_found(sbam_ctx *c, int64_t start, int32_t max_read_size) {
                  max_read_size, c->path.c_str(), (long long)start);
 }
 
-// h_* of a table whose copy the fast scan left in flight (sbam_scan_blocks)
-int host_blocks(sbam_ctx *c) {
-  if (!c->blk_pending) return SBAM_OK;
-  HIPCHK(c, hipEventSynchronize(c->blk_ev[1]));
-  const int64_t nb = c->nblocks;
-  const int64_t *st = reinterpret_cast<const int64_t *>(c->h_stage + 8), *uo = st + nb;
-  const int32_t *cs = reinterpret_cast<const int32_t *>(uo + nb + 1), *us = cs + nb;
-  c->h_bstart.assign(st, st + nb);
-  c->h_buoff.assign(uo, uo + nb + 1);
-  c->h_bc.assign(cs, cs + nb);
-  c->h_bu.assign(us, us + nb);
-  c->blk_pending = false;
-  return SBAM_OK;
-}
-// the scanned stream's uncompressed length (waits only for its own 8-byte copy)
-int block_total(sbam_ctx *c, int64_t *L) {
-  if (!c->blk_pending) {
-    *L = c->h_buoff[c->nblocks];
-    return SBAM_OK;
-  }
-  HIPCHK(c, hipEventSynchronize(c->blk_ev[0]));
-  *L = *reinterpret_cast<const int64_t *>(c->h_stage);
-  return SBAM_OK;
-}
-// a scanned block table, with its host copy in h_*
+// a scanned block table, with its host copy in c->blk's vectors
 int ensure_blocks(sbam_ctx *c) {
-  if (c->nblocks < 0) return set_err(c, SBAM_ERR_STATE, "sbam_scan_blocks has not run");
-  return host_blocks(c);
+  if (c->blk.n < 0) return set_err(c, SBAM_ERR_STATE, "sbam_scan_blocks has not run");
+  HIPCHK(c, c->blk.get());
+  return SBAM_OK;
 }
 int ensure_stream(sbam_ctx *c) {
   if (c->L < 0) return set_err(c, SBAM_ERR_STATE, "sbam_inflate has not run");
   if (c->nref < 0) return set_err(c, SBAM_ERR_STATE, "contig lengths unknown (sbam_header / sbam_set_contig_lengths)");
-  return host_blocks(c);
+  return ensure_blocks(c);
 }
 
 // block index whose (relative) start == q, or -1
 int64_t block_at(const sbam_ctx *c, int64_t q) {
-  auto it = std::lower_bound(c->h_bstart.begin(), c->h_bstart.end(), q);
-  if (it == c->h_bstart.end() || *it != q) return -1;
-  return it - c->h_bstart.begin();
+  const std::vector<int64_t> &st = c->blk.start;
+  auto it = std::lower_bound(st.begin(), st.end(), q);
+  if (it == st.end() || *it != q) return -1;
+  return it - st.begin();
 }
 sbam_pos pos_of(const sbam_ctx *c, int64_t x, int64_t *hint = nullptr) {
   // last block with uoff <= x and usize > 0 containing x; x at a block end normalises to (next, 0).  hint: the block
   // of the previous (smaller) query — the search gallops from it (split starts ascend: 4767 full binary searches
   // over a 3 MB table were 0.2 ms of host time per 10 GB step)
-  int64_t lo = 0, hi = c->nblocks;
-  if (hint && *hint >= 0 && *hint < c->nblocks && c->h_buoff[*hint] <= x) {
+  const BlockMirror &t = c->blk;
+  int64_t lo = 0, hi = t.n;
+  if (hint && *hint >= 0 && *hint < t.n && t.uoff[*hint] <= x) {
     int64_t step = 1;
     lo = *hint;
-    while (lo + step < c->nblocks && c->h_buoff[lo + step] <= x) {
+    while (lo + step < t.n && t.uoff[lo + step] <= x) {
       lo += step;
       step *= 2;
     }
-    hi = std::min(lo + step, c->nblocks);
+    hi = std::min(lo + step, t.n);
   }
-  auto it = std::upper_bound(c->h_buoff.begin() + lo, c->h_buoff.begin() + hi, x);
-  int64_t b = (it - c->h_buoff.begin()) - 1;
+  auto it = std::upper_bound(t.uoff.begin() + lo, t.uoff.begin() + hi, x);
+  int64_t b = (it - t.uoff.begin()) - 1;
   if (hint && b >= 0) *hint = b;
-  while (b >= 0 && b < c->nblocks && x >= c->h_buoff[b] + c->h_bu[b]) b++;
-  if (b < 0 || b >= c->nblocks) {
-    const int64_t endp = c->nblocks > 0 ? c->h_bstart[c->nblocks - 1] + c->h_bc[c->nblocks - 1] : 0;
+  while (b >= 0 && b < t.n && x >= t.uoff[b] + t.usize[b]) b++;
+  if (b < 0 || b >= t.n) {
+    const int64_t endp = t.n > 0 ? t.start[t.n - 1] + t.csize[t.n - 1] : 0;
     return sbam_pos{c->base + endp, 0, 0};
   }
-  return sbam_pos{c->base + c->h_bstart[b], (int32_t)(x - c->h_buoff[b]), 0};
-}
-
-int ensure_bitmap(sbam_ctx *c, int64_t x0, int64_t x1) {
-  const size_t words = (size_t)((x1 - (x0 & ~(int64_t)63) + 63) / 64) + 1;
-  if (words > c->bitmap_cap) {
-    if (c->d_bitmap && log_grow()) std::fprintf(stderr, "[sbam] grow bitmap %zu -> %zu words\n", c->bitmap_cap, words);
-    dfree(c->d_bitmap);
-    HIPCHK(c, dalloc(&c->d_bitmap, words));
-    c->bitmap_cap = words;
-  }
-  return SBAM_OK;
+  return sbam_pos{c->base + t.start[b], (int32_t)(x - t.uoff[b]), 0};
 }
 
 }  // namespace
@@ -306,11 +464,11 @@ int sbam_open(int device, const uint8_t *data, int64_t len, int64_t base_offset,
   c->file_size = file_size;
   HIPCHK(c, hipSetDevice(device));
   HIPCHK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  HIPCHK(c, ensure(&c->d_comp, &c->comp_cap, (size_t)len + kCompPad));
+  HIPCHK(c, c->d_comp.ensure((size_t)len + kCompPad));
   HIPCHK(c, hipMemsetAsync(c->d_comp + len, 0, kCompPad, c->stream));
   if (len) HIPCHK(c, hipMemcpyAsync(c->d_comp, data, (size_t)len, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, dalloc(&c->d_small, 64));
-  HIPCHK(c, dalloc(&c->d_counts, kCountsWords));
+  HIPCHK(c, c->d_small.ensure(64));
+  HIPCHK(c, c->d_counts.ensure(kCountsWords));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SBAM_OK;
 }
@@ -319,58 +477,16 @@ void sbam_close(sbam_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  dfree(c->d_comp);
-  dfree(c->d_ccnt);
-  dfree(c->d_tcnt);
-  dfree(c->d_coff2);
-  dfree(c->d_plist);
-  dfree(c->d_pfb);
-  dfree(c->d_pok);
-  dfree(c->d_nfb);
-  dfree(c->d_cand);
-  dfree(c->d_cc);
-  dfree(c->d_coff);
-  dfree(c->d_slots);
-  dfree(c->d_qa);
-  dfree(c->d_qb);
-  dfree(c->d_status);
-  dfree(c->d_found);
-  dfree(c->d_bstart);
-  dfree(c->d_buoff);
-  dfree(c->d_bh);
-  dfree(c->d_bc);
-  dfree(c->d_bu);
-  dfree(c->d_u);
-  dfree(c->d_lens);
-  dfree(c->d_bitmap);
-  dfree(c->d_pool);
-  dfree(c->d_arena);
-  dfree(c->d_tokbase);
-  dfree(c->d_slow);
-  dfree(c->d_icnt);
-  dfree(c->d_small);
-  dfree(c->d_counts);
-  dfree(c->d_sx);
-  dfree(c->d_se);
-  dfree(c->d_sn);
-  dfree(c->d_sb);
-  dfree(c->d_roff);
-  dfree(c->d_rcols);
-  dfree(c->d_foff);
-  dfree(c->d_fdata);
+  if (c->blk.copy_stream) (void)hipStreamSynchronize(c->blk.copy_stream);
   for (auto &kv : c->ev) {
     (void)hipEventDestroy(kv.second.first);
     (void)hipEventDestroy(kv.second.second);
   }
   for (hipEvent_t e : c->load_ev)
     if (e) (void)hipEventDestroy(e);
-  if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-  for (hipEvent_t e : c->blk_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-  if (c->h_stage) (void)hipHostFree(c->h_stage);
+  c->blk.destroy();
   if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  delete c;  // (the device buffers free themselves: this context's device is current, its streams were idle)
 }
 
 const sbam_error *sbam_last_error(const sbam_ctx *c) { return c ? &c->err : nullptr; }
@@ -385,7 +501,7 @@ int sbam_load(sbam_ctx *c, const uint8_t *data, int64_t len, int64_t base_offset
   if (!c || (!data && len > 0) || len < 0 || base_offset < 0 || file_size < base_offset + len) return SBAM_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));  // the previous window's work is done with d_comp
-  HIPCHK(c, ensure(&c->d_comp, &c->comp_cap, (size_t)len + kCompPad));
+  HIPCHK(c, c->d_comp.ensure((size_t)len + kCompPad));
   HIPCHK(c, hipMemsetAsync(c->d_comp + len, 0, kCompPad, c->stream));
   // in 8 MiB pieces with at most kInFlight queued: a multi-GB copy queued whole would hold the copy engine, and the
   // small copies of another context's kernels running meanwhile (results, tables) would wait behind it
@@ -416,72 +532,37 @@ int sbam_reserve(sbam_ctx *c, int64_t comp_bytes, int64_t n_blocks, int64_t ubyt
   if (!c || comp_bytes < 0 || n_blocks < 0 || ubytes < 0 || n_records < 0) return SBAM_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->copy_stream) HIPCHK(c, hipStreamSynchronize(c->copy_stream));
+  if (c->blk.copy_stream) HIPCHK(c, hipStreamSynchronize(c->blk.copy_stream));
+  if ((size_t)comp_bytes + kCompPad > c->d_comp.size()) {  // keep the resident bytes (sbam_load replaces them anyway)
+    DevBuf<uint8_t> p;
+    HIPCHK(c, p.ensure((size_t)comp_bytes + kCompPad));
+    if (c->D + kCompPad > 0) HIPCHK(c, hipMemcpy(p, c->d_comp, (size_t)c->D + kCompPad, hipMemcpyDeviceToDevice));
+    c->d_comp.swap(p);
+  }
   // Any stage buffer that grows is a fresh allocation whose contents are gone, so a context that has already run a
   // stage drops its stages (sbam_reset) when one grows: a later query re-runs them instead of reading uninitialised
   // device memory.  The resident compressed bytes and the contig lengths are kept.
   bool grew = false;
-  auto grow = [&](auto **p, size_t *cap, size_t n) {  // (a buffer never allocated held no stage's data)
-    grew |= *p != nullptr && *cap < std::max<size_t>(n, 1);
-    return ensure(p, cap, n);
-  };
-  if ((size_t)comp_bytes + kCompPad > c->comp_cap) {  // keep the resident bytes (sbam_load replaces them anyway)
-    uint8_t *p = nullptr;
-    HIPCHK(c, dalloc(&p, (size_t)comp_bytes + kCompPad));
-    if (c->D + kCompPad > 0) HIPCHK(c, hipMemcpy(p, c->d_comp, (size_t)c->D + kCompPad, hipMemcpyDeviceToDevice));
-    dfree(c->d_comp);
-    c->d_comp = p;
-    c->comp_cap = (size_t)comp_bytes + kCompPad;
-  }
-  const int64_t nchunks = (comp_bytes + kScanChunk - 1) / kScanChunk;
-  HIPCHK(c, grow(&c->d_cc, &c->cc_cap, nchunks));
-  HIPCHK(c, grow(&c->d_coff, &c->coff_cap, nchunks));
-  HIPCHK(c, grow(&c->d_slots, &c->slots_cap, (size_t)nchunks * kScanSlots));
+  HIPCHK(c, ensure_scan(c, comp_bytes, &grew));
   // candidates: every block's header plus the rare false positives inside payloads
-  HIPCHK(c, grow(&c->d_cand, &c->cand_cap, (size_t)(n_blocks + n_blocks / 8 + 1024)));
-  HIPCHK(c, grow(&c->d_bstart, &c->bcap[0], n_blocks + 1));
-  HIPCHK(c, grow(&c->d_bh, &c->bcap[1], n_blocks + 1));
-  HIPCHK(c, grow(&c->d_bc, &c->bcap[2], n_blocks + 1));
-  HIPCHK(c, grow(&c->d_bu, &c->bcap[3], n_blocks + 1));
-  HIPCHK(c, grow(&c->d_buoff, &c->bcap[4], n_blocks + 1 + (n_blocks + 255) / 256));  // (+ the scan's sums)
-  HIPCHK(c, grow(&c->d_u, &c->u_cap, (size_t)ubytes + kStreamPad));
-  HIPCHK(c, grow(&c->d_status, &c->status_cap, n_blocks));
-  HIPCHK(c, grow(&c->d_found, &c->found_cap, n_blocks));
-  HIPCHK(c, grow(&c->d_pool, &c->pool_cap, inflate_token_bytes(ubytes, n_blocks)));
-  if (inflate_arena_bytes(ubytes) > c->arena_cap) {
-    HIPCHK(c, grow(&c->d_arena, &c->arena_cap, inflate_arena_bytes(ubytes) + 1024));
-    c->arena_cap -= 1024;
-  }
-  HIPCHK(c, grow(&c->d_tokbase, &c->tokbase_cap, n_blocks));
-  HIPCHK(c, grow(&c->d_slow, &c->slow_cap, 2 * n_blocks));  // (the exact decoder's list, then the stored-only list)
-  grew |= c->d_bitmap != nullptr && (size_t)((ubytes + 63) / 64) + 1 > c->bitmap_cap;
-  if (int rc = ensure_bitmap(c, 0, ubytes)) return rc;
-  HIPCHK(c, grow(&c->d_tcnt, &c->tcnt_cap, (size_t)(4 * check_tiles(0, ubytes) + 8)));  // (x0 may add a tile)
-  if (n_records > 0) {  // the chain pass's PASS0 list (about one entry per record) and loadReads' offsets
+  HIPCHK(c, c->d_cand.ensure((size_t)(n_blocks + n_blocks / 8 + 1024), &grew));
+  HIPCHK(c, ensure_table(c, n_blocks, &grew));
+  HIPCHK(c, ensure_inflate(c, ubytes, n_blocks, &grew));
+  HIPCHK(c, ensure_check(c, 0, ubytes, &grew));
+  if (n_records > 0) {  // the chain pass's PASS0 list (about one entry per record) and loadReads' columns
     const size_t n = (size_t)(n_records + n_records / 8 + 4096);
-    HIPCHK(c, grow(&c->d_plist, &c->plist_cap, n));
-    HIPCHK(c, grow(&c->d_pfb, &c->pfb_cap, n));
-    HIPCHK(c, grow(&c->d_pok, &c->pok_cap, n));
-    HIPCHK(c, grow(&c->d_roff, &c->roff_cap, n));
-    // loadReads' columns (sbam_load_records: an int64 column and ten int32 ones, 256-B aligned)
-    const size_t stride = (n * 8 + 255) & ~(size_t)255, stride4 = (n * 4 + 255) & ~(size_t)255;
-    HIPCHK(c, grow(&c->d_rcols, &c->rcols_cap, stride + 10 * stride4));
+    HIPCHK(c, ensure_chain_list(c, n, &grew));
+    HIPCHK(c, ensure_record_columns(c, n, &grew));
   }
-  if (grew && (c->ncand >= 0 || c->nblocks >= 0 || c->L >= 0 || c->n_loaded >= 0)) return sbam_reset(c);
+  if (grew && any_stage_ran(c)) return sbam_reset(c);
   return SBAM_OK;
 }
 
 int sbam_reset(sbam_ctx *c) {
   if (!c) return SBAM_ERR_ARG;
-  c->ncand = -1;
-  c->nblocks = -1;
-  c->blk_pending = false;
-  c->L = -1;
-  c->inflate_slow = -1;
-  c->bm_valid = false;
-  c->n_loaded = -1;
-  c->f_n = -1;
+  const hipError_t e = drop_stages(c);
   c->err = sbam_error{};
+  HIPCHK(c, e);
   return SBAM_OK;
 }
 
@@ -498,10 +579,8 @@ double sbam_last_kernel_ms(sbam_ctx *c, const char *kernel) {
 static int scan_candidates(sbam_ctx *c) {
   if (c->ncand >= 0) return SBAM_OK;
   Timer t(c, "scan");
-  const int64_t nchunks = (c->D + kScanChunk - 1) / kScanChunk;
-  HIPCHK(c, ensure(&c->d_cc, &c->cc_cap, nchunks));
-  HIPCHK(c, ensure(&c->d_coff, &c->coff_cap, nchunks));
-  HIPCHK(c, ensure(&c->d_slots, &c->slots_cap, (size_t)nchunks * kScanSlots));
+  const int64_t nchunks = scan_chunks(c->D);
+  HIPCHK(c, ensure_scan(c, c->D));
   // one pass into per-chunk slots (+ counts, exact even past the slots); d_small[0] = total, [1] = overflow
   HIPCHK(c, launch_scan_slots(c->d_comp, c->D, c->d_cc, nchunks, c->d_slots, c->d_small + 1, c->stream));
   HIPCHK(c, launch_scan_prefix(c->d_cc, nchunks, c->d_coff, c->d_small, c->stream));
@@ -509,7 +588,7 @@ static int scan_candidates(sbam_ctx *c) {
   HIPCHK(c, hipMemcpyAsync(tot_ovf, c->d_small, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const int64_t total = tot_ovf[0];
-  HIPCHK(c, ensure(&c->d_cand, &c->cand_cap, total));
+  HIPCHK(c, c->d_cand.ensure(total));
   if (tot_ovf[1] == 0) {
     HIPCHK(c, launch_scan_compact(c->d_slots, c->d_cc, c->d_coff, nchunks, c->d_cand, c->stream));
   } else {  // a chunk with more than kScanSlots candidates (blocks under 2 KiB): the exact second pass
@@ -530,8 +609,8 @@ int sbam_find_block_starts(sbam_ctx *c, const int64_t *starts, int64_t n, int32_
     rel[i] = starts[i] - c->base;
     if (rel[i] < 0 || rel[i] > c->D) return set_err(c, SBAM_ERR_ARG, "split start %lld outside loaded bytes", (long long)starts[i]);
   }
-  HIPCHK(c, ensure(&c->d_qa, &c->qa_cap, (size_t)n));
-  HIPCHK(c, ensure(&c->d_qb, &c->qb_cap, (size_t)n));
+  HIPCHK(c, c->d_qa.ensure((size_t)n));
+  HIPCHK(c, c->d_qb.ensure((size_t)n));
   int64_t *d_q = c->d_qa, *d_o = c->d_qb;
   HIPCHK(c, hipMemcpyAsync(d_q, rel.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, launch_find_block_starts(c->d_comp, c->D, c->d_cand, c->ncand, d_q, n, nchk, d_o, c->stream));
@@ -553,6 +632,7 @@ int sbam_find_block_starts(sbam_ctx *c, const int64_t *starts, int64_t n, int32_
 int sbam_scan_blocks(sbam_ctx *c, int64_t *n_blocks) {
   if (!c) return SBAM_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, c->blk.invalidate());  // (no table until this scan has built one)
   int rc = scan_candidates(c);
   if (rc) return rc;
   int64_t start_rel = 0;
@@ -563,8 +643,6 @@ int sbam_scan_blocks(sbam_ctx *c, int64_t *n_blocks) {
     start_rel = o - c->base;
   }
   Timer t(c, "chain");
-  std::vector<int64_t> st;
-  std::vector<int32_t> hs, cs, us;
   int64_t first = 0;
   HIPCHK(c, launch_lower_bound(c->d_cand, c->ncand, start_rel, c->d_small, c->stream));
   HIPCHK(c, hipMemcpyAsync(&first, c->d_small, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
@@ -589,84 +667,41 @@ int sbam_scan_blocks(sbam_ctx *c, int64_t *n_blocks) {
     else if (code == 2) nb = si - first + 1;
     else fast = false;  // a candidate that is not the next header: walk exactly on the host
   }
-  c->h_bstart.clear();
-  c->h_bc.clear();
-  c->h_bu.clear();
-  if (c->copy_stream) HIPCHK(c, hipEventSynchronize(c->blk_ev[1]));  // (the last table's copy has read its columns)
-  HIPCHK(c, ensure(&c->d_bstart, &c->bcap[0], nb + 1));
-  HIPCHK(c, ensure(&c->d_bh, &c->bcap[1], nb + 1));
-  HIPCHK(c, ensure(&c->d_bc, &c->bcap[2], nb + 1));
-  HIPCHK(c, ensure(&c->d_bu, &c->bcap[3], nb + 1));
   if (fast) {
     // columns and offsets built on the device; the host's copy is queued behind them, not waited for
-    const int64_t nwg = (nb + 255) / 256;
-    HIPCHK(c, ensure(&c->d_buoff, &c->bcap[4], nb + 1 + nwg));
+    HIPCHK(c, ensure_table(c, nb));
     HIPCHK(c, launch_gather_blocks(c->d_cand, first, nb, c->d_bstart, c->d_bh, c->d_bc, c->d_bu, c->d_buoff + nb + 1,
                                    c->d_buoff, c->stream));
-    const size_t need = 8 + (size_t)nb * 8 + (size_t)(nb + 1) * 8 + (size_t)nb * 8;
-    if (c->stage_cap < need) {
-      HIPCHK(c, hipStreamSynchronize(c->stream));  // (an earlier table's copy may still target the old staging)
-      if (c->h_stage) (void)hipHostFree(c->h_stage);
-      c->h_stage = nullptr;
-      c->stage_cap = 0;
-      HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_stage), need + need / 8, hipHostMallocDefault));
-      c->stage_cap = need + need / 8;
-    }
-    for (hipEvent_t &e : c->blk_ev)
-      if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    int64_t *st = reinterpret_cast<int64_t *>(c->h_stage + 8), *uo = st + nb;
-    int32_t *cs = reinterpret_cast<int32_t *>(uo + nb + 1), *us = cs + nb;
-    HIPCHK(c, hipMemcpyAsync(c->h_stage, c->d_buoff + nb, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipEventRecord(c->blk_ev[0], c->stream));
-    HIPCHK(c, hipEventRecord(c->blk_ev[2], c->stream));
-    HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->blk_ev[2], 0));
-    HIPCHK(c, hipMemcpyAsync(uo, c->d_buoff, (nb + 1) * 8, hipMemcpyDeviceToHost, c->copy_stream));
-    if (nb) {
-      HIPCHK(c, hipMemcpyAsync(st, c->d_bstart, nb * 8, hipMemcpyDeviceToHost, c->copy_stream));
-      HIPCHK(c, hipMemcpyAsync(cs, c->d_bc, nb * 4, hipMemcpyDeviceToHost, c->copy_stream));
-      HIPCHK(c, hipMemcpyAsync(us, c->d_bu, nb * 4, hipMemcpyDeviceToHost, c->copy_stream));
-    }
-    HIPCHK(c, hipEventRecord(c->blk_ev[1], c->copy_stream));
-    c->blk_pending = true;
+    HIPCHK(c, c->blk.start_copy(c->d_bstart, c->d_buoff, c->d_bc, c->d_bu, nb, c->stream));
   } else {
     std::vector<Candidate> hc(c->ncand);
     HIPCHK(c, hipMemcpy(hc.data(), c->d_cand, c->ncand * sizeof(Candidate), hipMemcpyDeviceToHost));
     int64_t q = start_rel, i = first;
-    std::vector<int32_t> h_h;
+    std::vector<int64_t> st;
+    std::vector<int32_t> hs, cs, us;
     for (;;) {  // MetadataStream._advance, exactly (MetadataStream.scala:23-54)
       if (q + 18 > c->D) break;
       while (i < c->ncand && hc[i].pos < q) i++;
       if (i >= c->ncand || hc[i].pos != q) return header_parse_error(c, q);
       const Candidate &k = hc[i];
       if (!(k.flags & CAND_ISIZE) || (k.flags & CAND_EMPTY)) break;
-      c->h_bstart.push_back(k.pos);
-      c->h_bc.push_back(k.csize);
-      c->h_bu.push_back(k.isize);
-      h_h.push_back(k.hsize);
+      st.push_back(k.pos);
+      cs.push_back(k.csize);
+      us.push_back(k.isize);
+      hs.push_back(k.hsize);
       q += k.csize;
     }
-    nb = (int64_t)c->h_bstart.size();
-    HIPCHK(c, ensure(&c->d_bstart, &c->bcap[0], nb + 1));
-    HIPCHK(c, ensure(&c->d_bh, &c->bcap[1], nb + 1));
-    HIPCHK(c, ensure(&c->d_bc, &c->bcap[2], nb + 1));
-    HIPCHK(c, ensure(&c->d_bu, &c->bcap[3], nb + 1));
-    HIPCHK(c, hipMemcpy(c->d_bstart, c->h_bstart.data(), nb * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_bh, h_h.data(), nb * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_bc, c->h_bc.data(), nb * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_bu, c->h_bu.data(), nb * 4, hipMemcpyHostToDevice));
-    c->h_buoff.resize(nb + 1);
-    int64_t acc = 0;
-    for (int64_t b = 0; b < nb; b++) {
-      c->h_buoff[b] = acc;
-      acc += (c->h_bu[b] < 0) ? 0 : c->h_bu[b];
-    }
-    c->h_buoff[nb] = acc;
-    HIPCHK(c, ensure(&c->d_buoff, &c->bcap[4], nb + 1));
-    HIPCHK(c, hipMemcpyAsync(c->d_buoff, c->h_buoff.data(), (nb + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    nb = (int64_t)st.size();
+    HIPCHK(c, ensure_table(c, nb));
+    HIPCHK(c, hipMemcpy(c->d_bstart, st.data(), nb * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_bh, hs.data(), nb * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_bc, cs.data(), nb * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_bu, us.data(), nb * 4, hipMemcpyHostToDevice));
+    BlockMirror &t = c->blk;
+    t.fill(std::move(st), std::move(cs), std::move(us));
+    HIPCHK(c, hipMemcpyAsync(c->d_buoff, t.uoff.data(), (nb + 1) * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
-  c->nblocks = nb;
   if (n_blocks) *n_blocks = nb;
   return SBAM_OK;
 }
@@ -675,46 +710,34 @@ int sbam_get_blocks(sbam_ctx *c, int64_t *start, int32_t *csize, int32_t *usize,
   if (!c) return SBAM_ERR_ARG;
   int rc = ensure_blocks(c);
   if (rc) return rc;
-  if (cap < c->nblocks) return set_err(c, SBAM_ERR_ARG, "capacity %lld < %lld blocks", (long long)cap, (long long)c->nblocks);
-  for (int64_t b = 0; b < c->nblocks; b++) {
-    if (start) start[b] = c->base + c->h_bstart[b];
-    if (csize) csize[b] = c->h_bc[b];
-    if (usize) usize[b] = c->h_bu[b];
-    if (uoff) uoff[b] = c->h_buoff[b];
+  const BlockMirror &t = c->blk;
+  if (cap < t.n) return set_err(c, SBAM_ERR_ARG, "capacity %lld < %lld blocks", (long long)cap, (long long)t.n);
+  for (int64_t b = 0; b < t.n; b++) {
+    if (start) start[b] = c->base + t.start[b];
+    if (csize) csize[b] = t.csize[b];
+    if (usize) usize[b] = t.usize[b];
+    if (uoff) uoff[b] = t.uoff[b];
   }
   return SBAM_OK;
 }
 
 int sbam_inflate(sbam_ctx *c, int64_t *usz) {
   if (!c) return SBAM_ERR_ARG;
-  if (c->nblocks < 0) return set_err(c, SBAM_ERR_STATE, "sbam_scan_blocks has not run");
-  int rc = SBAM_OK;  // (the table's host copy is picked up below, while the decoder runs)
+  if (c->blk.n < 0) return set_err(c, SBAM_ERR_STATE, "sbam_scan_blocks has not run");
   HIPCHK(c, hipSetDevice(c->device));
   int64_t L = 0;
-  rc = block_total(c, &L);
-  if (rc) return rc;
-  HIPCHK(c, ensure(&c->d_u, &c->u_cap, (size_t)L + kStreamPad));
+  HIPCHK(c, c->blk.total(&L));  // (the table's host copy is picked up below, while the decoder runs)
+  const int64_t nb = c->blk.n;
+  HIPCHK(c, ensure_inflate(c, L, nb));
   HIPCHK(c, hipMemsetAsync(c->d_u + L, 0, kStreamPad, c->stream));
-  const int64_t nb = c->nblocks;
-  HIPCHK(c, ensure(&c->d_status, &c->status_cap, nb));
-  HIPCHK(c, ensure(&c->d_found, &c->found_cap, nb));
   int32_t *d_status = c->d_status, *d_found = c->d_found;
   const unsigned long long none = ~0ull;
   BlockTable bt{c->d_bstart, c->d_bh, c->d_bc, c->d_bu, c->d_buoff, nb};
-  // token pool (TokPool): main regions at 1 B per output byte, the arena for blocks that need more
-  HIPCHK(c, ensure(&c->d_pool, &c->pool_cap, inflate_token_bytes(L, nb)));
-  if (!c->d_arena || c->arena_cap < inflate_arena_bytes(L)) {
-    HIPCHK(c, ensure(&c->d_arena, &c->arena_cap, inflate_arena_bytes(L) + 1024));
-    c->arena_cap -= 1024;
-  }
-  HIPCHK(c, ensure(&c->d_tokbase, &c->tokbase_cap, nb));
-  HIPCHK(c, ensure(&c->d_slow, &c->slow_cap, 2 * nb));  // (the exact decoder's list, then the stored-only list)
-  if (!c->d_icnt) HIPCHK(c, dalloc(&c->d_icnt, 4));
   unsigned long long *d_used = reinterpret_cast<unsigned long long *>(c->d_small + 16);
   unsigned long long ferr = 0;
   unsigned int cnt3[3] = {0, 0, 0};  // slow-path blocks, -, blocks the resolver handed back
   for (;;) {
-    const TokPool tp{c->d_pool, c->d_arena, (int64_t)c->arena_cap, d_used, c->d_tokbase};
+    const TokPool tp{c->d_pool, c->arena.buf, (int64_t)c->arena.usable(), d_used, c->d_tokbase};
     HIPCHK(c, hipMemsetAsync(c->d_tokbase, 0xff, nb * sizeof(int64_t), c->stream));  // every block: main region
     HIPCHK(c, hipMemsetAsync(d_used, 0, sizeof(unsigned long long), c->stream));
     {
@@ -729,8 +752,7 @@ int sbam_inflate(sbam_ctx *c, int64_t *usz) {
     }
     // the table's host copy, while the kernels run (before the copies of the results below: copies into pageable
     // memory wait for the stream)
-    rc = host_blocks(c);
-    if (rc) return rc;
+    HIPCHK(c, c->blk.get());
     HIPCHK(c, hipMemcpyAsync(c->d_small + 2, &none, 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, launch_first_error(d_status, nb, reinterpret_cast<unsigned long long *>(c->d_small + 2), c->stream));
     HIPCHK(c, hipMemcpyAsync(&ferr, c->d_small + 2, 8, hipMemcpyDeviceToHost, c->stream));
@@ -749,23 +771,22 @@ int sbam_inflate(sbam_ctx *c, int64_t *usz) {
     unsigned long long used = 0;
     HIPCHK(c, hipMemcpy(&st, d_status + ferr, 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(&used, d_used, 8, hipMemcpyDeviceToHost));
-    if (st != 3 /* INF_OVERFLOW */ || used <= c->arena_cap) break;
+    if (st != 3 /* INF_OVERFLOW */ || used <= c->arena.usable()) break;
     // the arena was too small for the blocks that needed it (used counts every request): grow it, inflate again
-    if (log_grow()) std::fprintf(stderr, "[sbam] token arena %zu -> %llu bytes\n", c->arena_cap, used);
-    HIPCHK(c, ensure(&c->d_arena, &c->arena_cap, (size_t)used + (used >> 3) + 1024));
-    c->arena_cap -= 1024;
+    if (log_grow()) std::fprintf(stderr, "[sbam] token arena %zu -> %llu bytes\n", c->arena.usable(), used);
+    HIPCHK(c, c->arena.ensure((size_t)used + (used >> 3)));
   }
   c->inflate_slow = cnt3[0] + cnt3[2];
   if (ferr != ~0ull) {
     int32_t found = 0;
     HIPCHK(c, hipMemcpy(&found, d_found + ferr, 4, hipMemcpyDeviceToHost));
-    c->err.position = c->base + c->h_bstart[ferr];
-    c->err.expected = c->h_bu[ferr];
+    c->err.position = c->base + c->blk.start[ferr];
+    c->err.expected = c->blk.usize[ferr];
     c->err.actual = found;
-    return set_err(c, SBAM_ERR_INFLATE, "Expected %d decompressed bytes, found %d", c->h_bu[ferr], found);
+    return set_err(c, SBAM_ERR_INFLATE, "Expected %d decompressed bytes, found %d", c->blk.usize[ferr], found);
   }
   c->L = L;
-  c->bm_valid = false;
+  drop_bitmap(c);
   if (usz) *usz = L;
   return SBAM_OK;
 }
@@ -791,8 +812,8 @@ int sbam_pos_to_offset(sbam_ctx *c, sbam_pos p, int64_t *off) {
   int rc = ensure_blocks(c);
   if (rc) return rc;
   const int64_t b = block_at(c, p.block_pos - c->base);
-  if (b < 0 || p.offset < 0 || p.offset > c->h_bu[b]) return set_err(c, SBAM_ERR_ARG, "no block at %lld", (long long)p.block_pos);
-  *off = c->h_buoff[b] + p.offset;
+  if (b < 0 || p.offset < 0 || p.offset > c->blk.usize[b]) return set_err(c, SBAM_ERR_ARG, "no block at %lld", (long long)p.block_pos);
+  *off = c->blk.uoff[b] + p.offset;
   return SBAM_OK;
 }
 
@@ -808,12 +829,12 @@ int sbam_offset_to_pos(sbam_ctx *c, int64_t off, sbam_pos *p) {
 int sbam_set_contig_lengths(sbam_ctx *c, int32_t n_ref, const int64_t *lengths) {
   if (!c || n_ref < 0 || (n_ref && !lengths)) return SBAM_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, ensure(&c->d_lens, &c->lens_cap, (size_t)n_ref));
+  HIPCHK(c, c->d_lens.ensure((size_t)n_ref));
   if (n_ref) HIPCHK(c, hipMemcpyAsync(c->d_lens, lengths, n_ref * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->h_lens.assign(lengths, lengths + n_ref);
   c->nref = n_ref;
-  c->bm_valid = false;
+  drop_bitmap(c);
   return SBAM_OK;
 }
 
@@ -821,7 +842,7 @@ int sbam_header(sbam_ctx *c, int32_t *n_ref, int64_t *lengths, int32_t cap, sbam
   if (!c) return SBAM_ERR_ARG;
   if (c->L < 0) return set_err(c, SBAM_ERR_STATE, "sbam_inflate has not run");
   if (c->base != 0) return set_err(c, SBAM_ERR_STATE, "header lives in the file's first block (shard: sbam_set_contig_lengths)");
-  if (int rc = host_blocks(c)) return rc;
+  if (int rc = ensure_blocks(c)) return rc;
   auto rd = [&](int64_t off, int64_t n, void *dst) -> bool {
     if (off < 0 || off + n > c->L) return false;
     return hipMemcpy(dst, c->d_u + off, (size_t)n, hipMemcpyDeviceToHost) == hipSuccess;
@@ -882,32 +903,30 @@ static int check_range_args(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R) {
 }
 
 static hipError_t run_chains(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, int32_t by_key, CountsDev cd,
-                             const int32_t *tile_pass0 = nullptr);
+                             bool *list_form, const int32_t *tile_pass0 = nullptr);
 
 int sbam_check_eager(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, uint64_t *bitmap) {
   if (!c) return SBAM_ERR_ARG;
   int rc = check_range_args(c, x0, x1, R);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  rc = ensure_bitmap(c, x0, x1);
-  if (rc) return rc;
+  drop_bitmap(c);
+  HIPCHK(c, ensure_bitmap(c, x0, x1));
+  bool list_form = false;
   {
     Timer t(c, "check_eager");
     {
       Timer t0(c, "check_eager_pass0");
       HIPCHK(c, launch_check_eager_pass0(view(c), x0, x1, R, c->d_bitmap, c->stream));
     }
-    HIPCHK(c, run_chains(c, x0, x1, R, 0, CountsDev{}));
+    HIPCHK(c, run_chains(c, x0, x1, R, 0, CountsDev{}, &list_form));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (bitmap) {
     int rc2 = copy_bitmap_out(c, x0, x1, bitmap);
     if (rc2) return rc2;
   }
-  c->bm_x0 = x0 & ~(int64_t)63;
-  c->bm_x1 = x1;
-  c->bm_R = R;
-  c->bm_valid = true;
+  set_bitmap(c, x0, x1, R, list_form);
   return SBAM_OK;
 }
 
@@ -916,51 +935,41 @@ int sbam_check_full_words(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, uint32
   int rc = check_range_args(c, x0, x1, R);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  uint32_t *d_w = nullptr;
-  HIPCHK(c, dalloc(&d_w, x1 - x0));
-  rc = ensure_bitmap(c, x0, x1);
-  if (rc) return rc;
+  drop_bitmap(c);
+  DevBuf<uint32_t> d_w;  // (per-call: one word per position)
+  HIPCHK(c, d_w.ensure(x1 - x0));
+  HIPCHK(c, ensure_bitmap(c, x0, x1));
   {
     Timer t(c, "check_words");
     HIPCHK(c, launch_check_words(view(c), x0, x1, R, d_w, c->d_bitmap, c->stream));
   }
-  c->bm_list = false;
-  c->bm_x0 = x0 & ~(int64_t)63;
-  c->bm_x1 = x1;
-  c->bm_R = R;
-  c->bm_valid = true;
   if (x1 > x0) HIPCHK(c, hipMemcpyAsync(words, d_w, (x1 - x0) * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  dfree(d_w);
+  set_bitmap(c, x0, x1, R, false);
   return SBAM_OK;
 }
 
 // Chain pass after a record-0 pass: the list form (launch_chain_list_*) when the PASS0 positions fit its
-// scratch (a position list of up to 1/32 of the range), else the per-chunk k_chains walk.
+// scratch (a position list of up to 1/32 of the range), else the per-chunk k_chains walk.  *list_form: which one
+// built the bitmap (for set_bitmap).
 static hipError_t run_chains(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, int32_t by_key, CountsDev cd,
-                             const int32_t *tile_pass0) {
+                             bool *list_form, const int32_t *tile_pass0) {
   const int64_t nch = chain_list_chunks(x0, x1);
   const int64_t cap = (x1 - x0) / 32 + 4096;
-  hipError_t e;
-  if ((e = ensure(&c->d_ccnt, &c->ccnt_cap, (size_t)std::max<int64_t>(nch, 1))) != hipSuccess) return e;
-  if ((e = ensure(&c->d_coff2, &c->coff2_cap, (size_t)nch + 1)) != hipSuccess) return e;
+  HIPTRY(c->d_ccnt.ensure((size_t)std::max<int64_t>(nch, 1)));
+  HIPTRY(c->d_coff2.ensure((size_t)nch + 1));
   ChainScratch cs{c->d_ccnt, c->d_coff2, nullptr, nullptr, nullptr, nullptr};
-  if ((e = launch_chain_list_build(x0, x1, c->d_bitmap, cs, tile_pass0, c->stream)) != hipSuccess) return e;
+  HIPTRY(launch_chain_list_build(x0, x1, c->d_bitmap, cs, tile_pass0, c->stream));
   int64_t total = 0;
-  if ((e = hipMemcpyAsync(&total, c->d_coff2 + nch, 8, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return e;
-  if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return e;
-  c->bm_list = false;
-  if (total > cap) return launch_check_full_chains(view(c), x0, x1, R, by_key, cd, c->d_bitmap, c->stream);
-  const size_t n = (size_t)std::max<int64_t>(total, 1);
-  if ((e = ensure(&c->d_plist, &c->plist_cap, n)) != hipSuccess) return e;
-  if ((e = ensure(&c->d_pfb, &c->pfb_cap, n)) != hipSuccess) return e;
-  if ((e = ensure(&c->d_pok, &c->pok_cap, n)) != hipSuccess) return e;
-  if ((e = ensure(&c->d_nfb, &c->nfb_cap, 3)) != hipSuccess) return e;
+  HIPTRY(hipMemcpyAsync(&total, c->d_coff2 + nch, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPTRY(hipStreamSynchronize(c->stream));
+  *list_form = total <= cap;
+  if (!*list_form) return launch_check_full_chains(view(c), x0, x1, R, by_key, cd, c->d_bitmap, c->stream);
+  HIPTRY(ensure_chain_list(c, (size_t)std::max<int64_t>(total, 1)));
   cs.list = c->d_plist;
   cs.ok = c->d_pok;
   cs.fb = c->d_pfb;
   cs.n_fb = c->d_nfb;
-  c->bm_list = true;
   c->plist_n = total;
   return launch_chain_list_run(view(c), x0, x1, R, by_key, cd, c->d_bitmap, cs, c->stream);
 }
@@ -971,8 +980,8 @@ int sbam_check_full_counts(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, int32
   int rc = check_range_args(c, x0, x1, R);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  rc = ensure_bitmap(c, x0, x1);
-  if (rc) return rc;
+  drop_bitmap(c);
+  HIPCHK(c, ensure_check(c, x0, x1));
   HIPCHK(c, hipMemsetAsync(c->d_counts, 0, kCountsWords * 8, c->stream));
   CountsDev cd;
   cd.counts = c->d_counts;
@@ -981,9 +990,8 @@ int sbam_check_full_counts(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, int32
   cd.pair = cd.rbe + 21 * 128;
   cd.scalars = cd.pair + 19 * 19;
   cd.totals = cd.scalars + 4;
-  HIPCHK(c, ensure(&c->d_tcnt, &c->tcnt_cap, (size_t)std::max<int64_t>(4 * check_tiles(x0, x1), 1)));
   cd.tile_pass0 = c->d_tcnt;
-  bool tiles = false;
+  bool tiles = false, list_form = false;
   {
     Timer t(c, "check_full");
     {
@@ -991,7 +999,7 @@ int sbam_check_full_counts(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, int32
       HIPCHK(c, launch_check_full_counts(view(c), x0, x1, R, by_key, cd, c->d_bitmap, c->stream, &tiles));
     }
     Timer t1(c, "check_chains");
-    HIPCHK(c, run_chains(c, x0, x1, R, by_key, cd, tiles ? c->d_tcnt : nullptr));
+    HIPCHK(c, run_chains(c, x0, x1, R, by_key, cd, &list_form, tiles ? c->d_tcnt.get() : nullptr));
   }
   std::vector<unsigned long long> h(kCountsWords);
   HIPCHK(c, hipMemcpyAsync(h.data(), c->d_counts, kCountsWords * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1019,10 +1027,7 @@ int sbam_check_full_counts(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, int32
   out->n_halo = (int64_t)p[3];
   p += 4;
   for (int f = 0; f < 19; f++) out->totals[f] = (int64_t)p[f];
-  c->bm_x0 = x0 & ~(int64_t)63;
-  c->bm_x1 = x1;
-  c->bm_R = R;
-  c->bm_valid = true;
+  set_bitmap(c, x0, x1, R, list_form);
   if (out->n_halo) {
     c->err.actual = out->n_halo;
     return set_err(c, SBAM_ERR_HALO, "%lld positions need bytes past the shard", (long long)out->n_halo);
@@ -1035,14 +1040,14 @@ static int find_record_starts(sbam_ctx *c, const std::vector<int64_t> &x0, int32
   const int64_t n = (int64_t)x0.size();
   out.assign(n, -1);
   if (!n) return SBAM_OK;
-  HIPCHK(c, ensure(&c->d_qa, &c->qa_cap, (size_t)n));
-  HIPCHK(c, ensure(&c->d_qb, &c->qb_cap, (size_t)n));
+  HIPCHK(c, c->d_qa.ensure((size_t)n));
+  HIPCHK(c, c->d_qb.ensure((size_t)n));
   int64_t *d_x = c->d_qa, *d_o = c->d_qb;
   HIPCHK(c, hipMemcpyAsync(d_x, x0.data(), n * 8, hipMemcpyHostToDevice, c->stream));
   const bool bm = use_bm && c->bm_valid && c->bm_R == R;
   {
     Timer t(c, "find_record");
-    HIPCHK(c, launch_find_record_starts(view(c), d_x, n, R, mrs, bm ? c->d_bitmap : nullptr, c->bm_x0, c->bm_x1, d_o,
+    HIPCHK(c, launch_find_record_starts(view(c), d_x, n, R, mrs, bm ? c->d_bitmap.get() : nullptr, c->bm_x0, c->bm_x1, d_o,
                                         c->stream));
   }
   HIPCHK(c, hipMemcpyAsync(out.data(), d_o, n * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1059,7 +1064,7 @@ int sbam_find_record_start(sbam_ctx *c, int64_t block_start, int32_t R, int32_t 
   *found = 0;
   const int64_t b = block_at(c, block_start - c->base);
   if (b < 0) return SBAM_OK;  // EOF-marker block / past the stream: the uncompressed stream is empty → None
-  std::vector<int64_t> x0{c->h_buoff[b]}, out;
+  std::vector<int64_t> x0{c->blk.uoff[b]}, out;
   rc = find_record_starts(c, x0, R, mrs, true, out);
   if (rc) return rc;
   if (out[0] == -2) return set_err(c, SBAM_ERR_HALO, "record search left the shard");
@@ -1105,16 +1110,16 @@ static int split_starts(sbam_ctx *c, const sbam_split_args *a, int64_t first, in
   xe.assign(count, 0);
   // block_at / x_end_of for every split: the queries ascend, so each search gallops from the previous answer
   // (10 240 independent binary searches over the host block table took ~1 ms of host time per 10 GB step)
-  const int64_t nbh = (int64_t)c->h_bstart.size();
-  auto first_ge = [&](int64_t from, int64_t q) {  // first index >= from with h_bstart[index] >= q
+  const std::vector<int64_t> &bst = c->blk.start, &buo = c->blk.uoff;
+  const int64_t nbh = (int64_t)bst.size();
+  auto first_ge = [&](int64_t from, int64_t q) {  // first index >= from with bst[index] >= q
     int64_t lo = from, step = 1, hi = from;
-    while (hi < nbh && c->h_bstart[hi] < q) {
+    while (hi < nbh && bst[hi] < q) {
       lo = hi + 1;
       hi += step;
       step *= 2;
     }
-    return (int64_t)(std::lower_bound(c->h_bstart.begin() + lo, c->h_bstart.begin() + std::min(hi, nbh), q) -
-                     c->h_bstart.begin());
+    return (int64_t)(std::lower_bound(bst.begin() + lo, bst.begin() + std::min(hi, nbh), q) - bst.begin());
   };
   int64_t ib = 0, ie = 0;
   for (int64_t i = 0; i < count; i++) {
@@ -1122,12 +1127,12 @@ static int split_starts(sbam_ctx *c, const sbam_split_args *a, int64_t first, in
     const bool sorted = i == 0 || (bs[i] >= bs[i - 1] && en[first + i] >= en[first + i - 1]);
     ib = first_ge(sorted ? ib : 0, qb);
     ie = first_ge(sorted ? ie : 0, qe);
-    const int64_t b = (ib < nbh && c->h_bstart[ib] == qb) ? ib : -1;  // block_at
+    const int64_t b = (ib < nbh && bst[ib] == qb) ? ib : -1;  // block_at
     if (b < 0) {  // FindRecordStart on the EOF marker: empty stream → None → NoReadFoundException
       return no_read_found(c, bs[i], a->max_read_size);
     }
-    x0[i] = c->h_buoff[b];
-    xe[i] = ie < nbh ? c->h_buoff[ie] : c->L;  // flat offset of Pos(first block starting at or past the end, 0)
+    x0[i] = buo[b];
+    xe[i] = ie < nbh ? buo[ie] : c->L;  // flat offset of Pos(first block starting at or past the end, 0)
   }
   rc = find_record_starts(c, x0, a->reads_to_check, a->max_read_size, a->use_success_bitmap != 0, xs);
   if (rc) return rc;
@@ -1149,9 +1154,9 @@ static int split_counts(sbam_ctx *c, bool try_bitmap, const std::vector<int64_t>
   *proved = false;
   cnt.assign(n, 0);
   if (!n) return SBAM_OK;
-  HIPCHK(c, ensure(&c->d_sx, &c->sx_cap, n));
-  HIPCHK(c, ensure(&c->d_se, &c->se_cap, n));
-  HIPCHK(c, ensure(&c->d_sn, &c->sn_cap, n));
+  HIPCHK(c, c->d_sx.ensure(n));
+  HIPCHK(c, c->d_se.ensure(n));
+  HIPCHK(c, c->d_sn.ensure(n));
   HIPCHK(c, hipMemcpyAsync(c->d_sx, xs.data(), n * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_se, xe.data(), n * 8, hipMemcpyHostToDevice, c->stream));
   const int64_t X0 = *std::min_element(xs.begin(), xs.end());
@@ -1166,9 +1171,9 @@ static int split_counts(sbam_ctx *c, bool try_bitmap, const std::vector<int64_t>
     const char *fp = std::getenv("SBAM_FORCE_PROOF");
     const bool force = fp && *fp && *fp != '0';
     HIPCHK(c, launch_chain_proof(c->d_u, c->L, c->d_bitmap, xa, X0, X1, d_fail,
-                                 (c->bm_list && !force) ? c->d_nfb : nullptr, c->stream));
+                                 (c->bm_list && !force) ? c->d_nfb.get() : nullptr, c->stream));
     HIPCHK(c, launch_split_popcounts(c->d_bitmap, xa, c->d_sx, c->d_se, n, c->d_sn, d_fail, c->d_plist, c->plist_n,
-                                     c->bm_list ? c->d_nfb : nullptr, c->stream));
+                                     c->bm_list ? c->d_nfb.get() : nullptr, c->stream));
     int32_t fail = 1;
     HIPCHK(c, hipMemcpyAsync(&fail, d_fail, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(cnt.data(), c->d_sn, n * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1235,15 +1240,14 @@ int sbam_record_offsets(sbam_ctx *c, int64_t x0, int64_t x_end, int64_t *offsets
   int rc = ensure_stream(c);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  int64_t *d_o = nullptr;
-  HIPCHK(c, dalloc(&d_o, cap));
+  DevBuf<int64_t> d_o;  // (per-call)
+  HIPCHK(c, d_o.ensure(cap));
   HIPCHK(c, launch_record_offsets(view(c), x0, std::min(x_end, c->L), d_o, cap, c->d_small + 4, c->stream));
   int64_t n = 0;
   HIPCHK(c, hipMemcpyAsync(&n, c->d_small + 4, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (n < 0) n = -(n + 3);
   if (offsets && n) HIPCHK(c, hipMemcpy(offsets, d_o, std::min(n, cap) * 8, hipMemcpyDeviceToHost));
-  dfree(d_o);
   *n_out = n;
   return SBAM_OK;
 }
@@ -1254,18 +1258,16 @@ int sbam_record_spans(sbam_ctx *c, const int64_t *offsets, int64_t n, int32_t *r
   int rc = ensure_stream(c);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  int64_t *d_o = nullptr;
-  int32_t *d_r = nullptr;
-  HIPCHK(c, dalloc(&d_o, n));
-  HIPCHK(c, dalloc(&d_r, 3 * n));
+  DevBuf<int64_t> d_o;  // (per-call)
+  DevBuf<int32_t> d_r;
+  HIPCHK(c, d_o.ensure(n));
+  HIPCHK(c, d_r.ensure(3 * n));
   HIPCHK(c, hipMemcpyAsync(d_o, offsets, n * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, launch_record_spans(c->d_u, c->L, d_o, n, d_r, d_r + n, d_r + 2 * n, c->stream));
   HIPCHK(c, hipMemcpyAsync(ref_id, d_r, n * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(start, d_r + n, n * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(end, d_r + 2 * n, n * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  dfree(d_o);
-  dfree(d_r);
   return SBAM_OK;
 }
 
@@ -1287,22 +1289,8 @@ int sbam_load_records(sbam_ctx *c, const sbam_split_args *a, int64_t first, int6
   std::vector<int64_t> base(count + 1, 0);
   for (int64_t i = 0; i < count; i++) base[i + 1] = base[i] + cnt[i];
   const int64_t N = base[count];
-  HIPCHK(c, ensure(&c->d_sb, &c->sb_cap, count + 1));
-  HIPCHK(c, ensure(&c->d_roff, &c->roff_cap, N));
-  // column arena: block_pos (8 B) + 10 × 4 B, each column 256-B aligned
-  const size_t stride = ((size_t)std::max<int64_t>(N, 1) * 8 + 255) & ~(size_t)255;
-  const size_t stride4 = ((size_t)std::max<int64_t>(N, 1) * 4 + 255) & ~(size_t)255;
-  HIPCHK(c, ensure(&c->d_rcols, &c->rcols_cap, stride + 10 * stride4));
-  {
-    uint8_t *p = c->d_rcols;
-    RecordColumnsDev &k = c->rcols;
-    k.block_pos = reinterpret_cast<int64_t *>(p);
-    int32_t *q[10];
-    for (int j = 0; j < 10; j++) q[j] = reinterpret_cast<int32_t *>(p + stride + j * stride4);
-    k.block_off = q[0]; k.block_size = q[1]; k.ref_id = q[2]; k.pos = q[3];
-    k.bin_mq_nl = reinterpret_cast<uint32_t *>(q[4]); k.flag_nc = reinterpret_cast<uint32_t *>(q[5]);
-    k.l_seq = q[6]; k.next_ref_id = q[7]; k.next_pos = q[8]; k.tlen = q[9];
-  }
+  HIPCHK(c, c->d_sb.ensure(count + 1));
+  HIPCHK(c, ensure_record_columns(c, N, nullptr, &c->rcols));
   HIPCHK(c, hipMemcpyAsync(c->d_sb, base.data(), (count + 1) * 8, hipMemcpyHostToDevice, c->stream));
   {
     Timer t(c, "load_records");
@@ -1311,7 +1299,7 @@ int sbam_load_records(sbam_ctx *c, const sbam_split_args *a, int64_t first, int6
                                      c->stream));
     else
       HIPCHK(c, launch_record_walk(c->d_u, c->L, c->d_sx, c->d_se, c->d_sb, count, c->d_roff, c->stream));
-    HIPCHK(c, launch_record_columns(c->d_u, c->d_roff, N, c->d_bstart, c->d_buoff, c->d_bu, c->nblocks, c->base,
+    HIPCHK(c, launch_record_columns(c->d_u, c->d_roff, N, c->d_bstart, c->d_buoff, c->d_bu, c->blk.n, c->base,
                                     c->rcols, c->stream));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1376,7 +1364,7 @@ int sbam_load_record_fields(sbam_ctx *c, int64_t i0, int64_t n, uint32_t fields,
   // offsets arena: four int64 columns of n + 1, the scan's per-workgroup sums, first bad record + four totals
   auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t ostride = up((size_t)(n + 1) * 8), nblk = (size_t)field_size_blocks(n);
-  HIPCHK(c, ensure(&c->d_foff, &c->foff_cap, 4 * ostride + up(4 * nblk * 8) + 256));
+  HIPCHK(c, c->d_foff.ensure(4 * ostride + up(4 * nblk * 8) + 256));
   int64_t *off[4];
   for (int f = 0; f < 4; f++) off[f] = reinterpret_cast<int64_t *>(c->d_foff + f * ostride);
   int64_t *bsum = reinterpret_cast<int64_t *>(c->d_foff + 4 * ostride);
@@ -1413,7 +1401,7 @@ int sbam_load_record_fields(sbam_ctx *c, int64_t i0, int64_t n, uint32_t fields,
     tiles_at[f] = need;
     need += up((size_t)field_gather_tiles(col[f].bytes) * 16);
   }
-  HIPCHK(c, ensure(&c->d_fdata, &c->fdata_cap, need));
+  HIPCHK(c, c->d_fdata.ensure(need));
   uint8_t *data[5];
   {
     Timer t(c, "record_fields");

@@ -160,6 +160,117 @@ def test_reserve_after_run_drops_stages_gpu():
 
 
 @pytest.mark.gpu
+def test_reserve_on_scan_only_context_gpu():
+    """A context that was scanned but not inflated, then reserved at twice every size: the growing block-table
+    buffers drop the scan in the C context (sbam_get_blocks is SBAM_ERR_STATE) and BamFile.reserve runs it again, so
+    blocks() and a later inflate() equal a fresh context's; a reserve that grows nothing leaves the scan in place."""
+    import numpy as np
+    import sbam
+    from conftest import fixture_bytes
+    a = fixture_bytes("2.bam")
+    with sbam.BamFile(a) as fresh:
+        want_blocks = [x.copy() for x in fresh.blocks()]
+        want_calls = fresh.check_eager(0, fresh.uncompressed_size)
+        L_, nb = int(fresh.uncompressed_size), int(fresh.n_blocks)
+    sizes = (2 * len(a), 2 * nb, 2 * L_, 2 * int(want_calls.sum()))
+    L = sbam.load_library()
+    with sbam.BamFile(a, inflate=False) as f:
+        f.reserve(*sizes)
+        assert f.n_blocks == nb and f.uncompressed_size is None
+        assert all(np.array_equal(x, y) for x, y in zip(f.blocks(), want_blocks))
+        assert f.inflate() == L_
+        f.header()  # (a context opened without inflate has no contig lengths yet)
+        assert np.array_equal(f.check_eager(0, L_), want_calls)
+        # nothing grows: scan and stream stay (a 0-capacity query of an intact table is an argument error)
+        f.reserve(*sizes)
+        assert L.sbam_get_blocks(f.ctx, None, None, None, None, 0) == sbam.ERR_ARG
+        assert L.sbam_read_uncompressed(f.ctx, 0, 0, None) == sbam.SBAM_OK
+    with sbam.BamFile(a, inflate=False) as g:  # raw ABI: the grown context reports that the scan has to run again
+        assert L.sbam_get_blocks(g.ctx, None, None, None, None, 0) == sbam.ERR_ARG
+        assert L.sbam_reserve(g.ctx, *sizes) == sbam.SBAM_OK
+        assert L.sbam_get_blocks(g.ctx, None, None, None, None, 0) == sbam.ERR_STATE
+
+
+_RESERVED_CHILD = """
+import sys
+import sbam
+a, b = (open(p, "rb").read() for p in sys.argv[1:3])
+with sbam.BamFile(a) as f:
+    f.reserve(*map(int, sys.argv[3:7]))
+    sys.stderr.write("reserved\\n")
+    sys.stderr.flush()
+    f.load(b)
+    f.run()
+    c = f.check_full_counts()
+    try:
+        f.compute_splits(64 << 10)
+        raise SystemExit("64 KiB splits: expected NoReadFoundException")
+    except sbam.NoReadFoundException:
+        pass
+    splits = f.compute_splits(100000)
+    sizes, _ = f.load_records(100000)
+    print(f.n_blocks, f.uncompressed_size, c.n_success, len(splits), int(sizes.sum()))
+"""
+
+
+@pytest.mark.gpu
+def test_reserved_context_does_not_reallocate_gpu():
+    """One size rule per stage: a context opened on 1.bam and reserved with 2.bam's compressed size, block count,
+    uncompressed size and record count runs 2.bam (scan, inflate, full check, splits, loadReads) without replacing
+    a device buffer: with SBAM_LOG_GROW=1 nothing is reported after the reserve.  (A child process: the switch is
+    read once per process.)  2.bam's last 64 KiB Hadoop split starts behind its last data block, so computing splits
+    at 64 KiB ends in the reference's NoReadFoundException, here as on a fresh context (after FindBlockStart has
+    run); splits and loadReads then run at 100000 bytes, where every split holds records."""
+    import subprocess
+    import sys
+    import sbam
+    from conftest import FIXTURES, fixture_bytes
+    b = fixture_bytes("2.bam")
+    with sbam.BamFile(b) as fresh:
+        c = fresh.check_full_counts()
+        with pytest.raises(sbam.NoReadFoundException):
+            fresh.compute_splits(64 << 10)
+        splits = fresh.compute_splits(100000)
+        sizes, _ = fresh.load_records(100000)
+        want = (fresh.n_blocks, fresh.uncompressed_size, c.n_success, len(splits), int(sizes.sum()))
+    env = dict(os.environ, SBAM_LOG_GROW="1", PYTHONPATH=os.path.join(ROOT, "spark-bam_amd"))
+    p = subprocess.run([sys.executable, "-c", _RESERVED_CHILD, os.path.join(FIXTURES, "1.bam"),
+                        os.path.join(FIXTURES, "2.bam"), str(len(b)), str(want[0]), str(want[1]), str(want[4])],
+                       env=env, capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr
+    assert tuple(map(int, p.stdout.split())) == want
+    assert "reserved\n" in p.stderr
+    after = p.stderr.split("reserved\n", 1)[1]
+    assert "[sbam] grow" not in after and "token arena" not in after, after
+
+
+@pytest.mark.gpu
+def test_close_and_reopen_gpu():
+    """Contexts opened, run and closed 20 times in one process (each frees every buffer it owns, after its streams
+    are idle), the per-call scratch of the words / record-offset / record-span entry points included; a
+    sbam_check_full_words that fails its argument check (x1 > L) leaves a context that closes, and a fresh context
+    still gives 1.bam's 4917 record starts."""
+    import numpy as np
+    import sbam
+    from conftest import fixture_bytes
+    a = fixture_bytes("1.bam")
+    L = sbam.load_library()
+    for _ in range(20):
+        with sbam.BamFile(a) as f:
+            assert f.blocks()[0].size == 25
+    with sbam.BamFile(a) as f:
+        n = f.uncompressed_size
+        w = f.check_full_words(0, n)
+        assert int(((w & sbam.WORD_SUCCESS) != 0).sum()) == 4917
+        offs = f.record_offsets(int(np.flatnonzero(w & sbam.WORD_SUCCESS)[0]), n)
+        assert offs.size == 4917 and f.record_spans(offs)[0].size == 4917
+        out = np.zeros(n + 1, np.uint32)
+        assert L.sbam_check_full_words(f.ctx, 0, n + 1, 10, out.ctypes.data) == sbam.ERR_ARG
+    with sbam.BamFile(a) as f:
+        assert int(f.check_eager(0, f.uncompressed_size).sum()) == 4917
+
+
+@pytest.mark.gpu
 def test_load_window_gpu():
     """sbam_load: a context re-filled with another file (and back) gives the same blocks, stream and checker
     calls as a fresh sbam_open of that file, with its allocations reused."""
