@@ -161,15 +161,44 @@ class RecordFields:
     aux: Optional[np.ndarray] = None
 
 
-EXPORTS = [  # every symbol include/sbam.h declares
-    "sbam_open", "sbam_close", "sbam_load", "sbam_reserve", "sbam_last_error", "sbam_set_path", "sbam_reset", "sbam_version", "sbam_find_block_starts", "sbam_scan_blocks",
-    "sbam_get_blocks", "sbam_inflate", "sbam_inflate_fallbacks", "sbam_read_uncompressed", "sbam_pos_to_offset", "sbam_offset_to_pos",
-    "sbam_header", "sbam_set_contig_lengths", "sbam_check_eager", "sbam_check_full_words", "sbam_check_full_counts",
-    "sbam_find_record_start", "sbam_file_splits", "sbam_split_records", "sbam_compute_splits",
-    "sbam_record_offsets", "sbam_record_spans", "sbam_load_records", "sbam_get_record_columns", "sbam_record_columns_device",
-    "sbam_load_record_fields", "sbam_get_record_fields", "sbam_record_fields_device",
-    "sbam_last_kernel_ms",
-]
+_vp, _i64, _i32, _P = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER
+_SIGNATURES = {  # (restype, argtypes) of every symbol include/sbam.h declares
+    "sbam_open": (ctypes.c_int, [ctypes.c_int, _vp, _i64, _i64, _i64, _P(_vp)]),
+    "sbam_close": (None, [_vp]),
+    "sbam_last_error": (_P(_Error), [_vp]),
+    "sbam_set_path": (ctypes.c_int, [_vp, ctypes.c_char_p]),
+    "sbam_reset": (ctypes.c_int, [_vp]),
+    "sbam_version": (ctypes.c_char_p, []),
+    "sbam_find_block_starts": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "sbam_scan_blocks": (ctypes.c_int, [_vp, _P(_i64)]),
+    "sbam_get_blocks": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64]),
+    "sbam_inflate": (ctypes.c_int, [_vp, _P(_i64)]),
+    "sbam_inflate_fallbacks": (ctypes.c_int, [_vp, _P(_i64)]),
+    "sbam_read_uncompressed": (ctypes.c_int, [_vp, _i64, _i64, _vp]),
+    "sbam_pos_to_offset": (ctypes.c_int, [_vp, _Pos, _P(_i64)]),
+    "sbam_offset_to_pos": (ctypes.c_int, [_vp, _i64, _P(_Pos)]),
+    "sbam_header": (ctypes.c_int, [_vp, _P(_i32), _vp, _i32, _P(_Pos)]),
+    "sbam_set_contig_lengths": (ctypes.c_int, [_vp, _i32, _vp]),
+    "sbam_check_eager": (ctypes.c_int, [_vp, _i64, _i64, _i32, _vp]),
+    "sbam_check_full_words": (ctypes.c_int, [_vp, _i64, _i64, _i32, _vp]),
+    "sbam_check_full_counts": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _P(_Counts), _vp]),
+    "sbam_find_record_start": (ctypes.c_int, [_vp, _i64, _i32, _i32, _P(_i32), _P(_Pos), _P(_i32)]),
+    "sbam_file_splits": (ctypes.c_int, [_i64, _i64, _vp, _vp, _i64, _P(_i64)]),
+    "sbam_split_records": (ctypes.c_int, [_vp, _P(_SplitArgs), _i64, _i64, _vp, _vp, _vp]),
+    "sbam_compute_splits": (ctypes.c_int, [_vp, _P(_SplitArgs), _vp, _i64, _P(_i64)]),
+    "sbam_record_offsets": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _P(_i64)]),
+    "sbam_load": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64]),
+    "sbam_reserve": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64]),
+    "sbam_record_spans": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "sbam_load_records": (ctypes.c_int, [_vp, _P(_SplitArgs), _i64, _i64, _vp, _P(_i64)]),
+    "sbam_get_record_columns": (ctypes.c_int, [_vp, _i64, _i64, _P(_RecordColumns)]),
+    "sbam_record_columns_device": (ctypes.c_int, [_vp, _P(_RecordColumns), _P(_i64)]),
+    "sbam_load_record_fields": (ctypes.c_int, [_vp, _i64, _i64, ctypes.c_uint32, _P(_RecordFieldTotals)]),
+    "sbam_get_record_fields": (ctypes.c_int, [_vp, _P(_RecordFields)]),
+    "sbam_record_fields_device": (ctypes.c_int, [_vp, _P(_RecordFields), _P(_i64), _P(_i64)]),
+    "sbam_last_kernel_ms": (ctypes.c_double, [_vp, ctypes.c_char_p]),
+}
+EXPORTS = list(_SIGNATURES)
 
 _lib = None
 
@@ -195,44 +224,7 @@ def load_library(path: str = LIB_PATH):
     if not os.path.exists(path):
         raise ImportError(f"libsbam.so not built at {path}: run `make -C spark-bam_amd` (no CPU fallback exists)")
     L = ctypes.CDLL(os.path.abspath(path))
-    vp, i64, i32, P = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER
-    sig = {
-        "sbam_open": (ctypes.c_int, [ctypes.c_int, vp, i64, i64, i64, P(vp)]),
-        "sbam_close": (None, [vp]),
-        "sbam_last_error": (P(_Error), [vp]),
-        "sbam_set_path": (ctypes.c_int, [vp, ctypes.c_char_p]),
-        "sbam_reset": (ctypes.c_int, [vp]),
-        "sbam_version": (ctypes.c_char_p, []),
-        "sbam_find_block_starts": (ctypes.c_int, [vp, vp, i64, i32, vp]),
-        "sbam_scan_blocks": (ctypes.c_int, [vp, P(i64)]),
-        "sbam_get_blocks": (ctypes.c_int, [vp, vp, vp, vp, vp, i64]),
-        "sbam_inflate": (ctypes.c_int, [vp, P(i64)]),
-        "sbam_inflate_fallbacks": (ctypes.c_int, [vp, P(i64)]),
-        "sbam_read_uncompressed": (ctypes.c_int, [vp, i64, i64, vp]),
-        "sbam_pos_to_offset": (ctypes.c_int, [vp, _Pos, P(i64)]),
-        "sbam_offset_to_pos": (ctypes.c_int, [vp, i64, P(_Pos)]),
-        "sbam_header": (ctypes.c_int, [vp, P(i32), vp, i32, P(_Pos)]),
-        "sbam_set_contig_lengths": (ctypes.c_int, [vp, i32, vp]),
-        "sbam_check_eager": (ctypes.c_int, [vp, i64, i64, i32, vp]),
-        "sbam_check_full_words": (ctypes.c_int, [vp, i64, i64, i32, vp]),
-        "sbam_check_full_counts": (ctypes.c_int, [vp, i64, i64, i32, i32, P(_Counts), vp]),
-        "sbam_find_record_start": (ctypes.c_int, [vp, i64, i32, i32, P(i32), P(_Pos), P(i32)]),
-        "sbam_file_splits": (ctypes.c_int, [i64, i64, vp, vp, i64, P(i64)]),
-        "sbam_split_records": (ctypes.c_int, [vp, P(_SplitArgs), i64, i64, vp, vp, vp]),
-        "sbam_compute_splits": (ctypes.c_int, [vp, P(_SplitArgs), vp, i64, P(i64)]),
-        "sbam_record_offsets": (ctypes.c_int, [vp, i64, i64, vp, i64, P(i64)]),
-        "sbam_load": (ctypes.c_int, [vp, vp, i64, i64, i64]),
-        "sbam_reserve": (ctypes.c_int, [vp, i64, i64, i64, i64]),
-        "sbam_record_spans": (ctypes.c_int, [vp, vp, i64, vp, vp, vp]),
-        "sbam_load_records": (ctypes.c_int, [vp, P(_SplitArgs), i64, i64, vp, P(i64)]),
-        "sbam_get_record_columns": (ctypes.c_int, [vp, i64, i64, P(_RecordColumns)]),
-        "sbam_record_columns_device": (ctypes.c_int, [vp, P(_RecordColumns), P(i64)]),
-        "sbam_load_record_fields": (ctypes.c_int, [vp, i64, i64, ctypes.c_uint32, P(_RecordFieldTotals)]),
-        "sbam_get_record_fields": (ctypes.c_int, [vp, P(_RecordFields)]),
-        "sbam_record_fields_device": (ctypes.c_int, [vp, P(_RecordFields), P(i64), P(i64)]),
-        "sbam_last_kernel_ms": (ctypes.c_double, [vp, ctypes.c_char_p]),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in _SIGNATURES.items():
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
@@ -294,9 +286,35 @@ class Counts:
     n_success: int
     n_too_few_fixed: int
 
+    # the packed int64 vector (what ranks all_reduce, and what tests/golden/bench_digests.json pins): fields in this order
+    LAYOUT = (("totals", (19,)), ("by_key", (21, 19)), ("positions", (21,)), ("reads_before_error", (21, 128)),
+              ("pair_hist", (19, 19)), ("n_success", ()), ("n_too_few_fixed", ()), ("n_positions", ()))
+
     def total_error_counts(self) -> dict:
         t = self.totals
         return {FLAG_NAMES[i]: int(t[i]) for i in range(19)}
+
+    def pack(self) -> np.ndarray:
+        return np.concatenate([np.asarray(getattr(self, name), np.int64).ravel() for name, _ in self.LAYOUT])
+
+    @classmethod
+    def unpack(cls, v: np.ndarray) -> "Counts":
+        out, o = {}, 0
+        for name, shape in cls.LAYOUT:
+            n = int(np.prod(shape, dtype=np.int64))
+            out[name] = v[o:o + n].reshape(shape) if shape else int(v[o])
+            o += n
+        return cls(**out)
+
+    @classmethod
+    def zero(cls) -> "Counts":
+        return cls.unpack(np.zeros(N_COUNT_WORDS, np.int64))
+
+    def __add__(self, other: "Counts") -> "Counts":
+        return Counts(**{name: getattr(self, name) + getattr(other, name) for name, _ in self.LAYOUT})
+
+
+N_COUNT_WORDS = sum(int(np.prod(shape, dtype=np.int64)) for _, shape in Counts.LAYOUT)
 
 
 def n_hadoop_splits(file_size: int, split_size: int) -> int:
@@ -339,6 +357,7 @@ class BamFile:
         self.n_ref = None
         self.contig_lengths = None
         self.header_end = None
+        self.n_loaded = 0  # records of the last load_records still on the device
         if inflate:
             self.inflate()
             if contig_lengths is not None:
@@ -386,6 +405,7 @@ class BamFile:
             self.n_ref = self.contig_lengths = self.header_end = None
         self.n_blocks = None
         self.uncompressed_size = None
+        self.n_loaded = 0
 
     def reserve(self, comp_bytes: int, n_blocks: int, ubytes: int, n_records: int = 0):
         """sbam_reserve: size the device buffers for windows up to these sizes, so no later load reallocates.  A
@@ -396,6 +416,7 @@ class BamFile:
         had_scan, had_stream = self.n_blocks is not None, self.uncompressed_size is not None
         self._check(self.L.sbam_reserve(self.ctx, int(comp_bytes), int(n_blocks), int(ubytes), int(n_records)))
         if had_scan and self.L.sbam_get_blocks(self.ctx, None, None, None, None, 0) == ERR_STATE:
+            self.n_loaded = 0
             self.n_blocks = self._scan()
         if had_stream and self.L.sbam_read_uncompressed(self.ctx, 0, 0, None) == ERR_STATE:
             self.inflate()
@@ -410,6 +431,7 @@ class BamFile:
         self._check(self.L.sbam_reset(self.ctx))
         self.n_blocks = None
         self.uncompressed_size = None
+        self.n_loaded = 0
 
     def run(self, contig_lengths: Optional[Sequence[int]] = None):
         """Scan → inflate → header/contig lengths from the resident compressed bytes."""
@@ -638,7 +660,7 @@ class BamFile:
         columns; with host=False it holds only the totals and the columns stay on the device
         (sbam_record_fields_device)."""
         if n is None:
-            n = max(getattr(self, "n_loaded", 0) - i0, 0)
+            n = max(self.n_loaded - i0, 0)
         mask = 0
         for f in fields:
             if f not in FIELD_BITS:

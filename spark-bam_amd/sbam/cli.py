@@ -37,7 +37,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 
 import sbam
-from sbam import FLAG_NAMES, Pos
+from sbam import FLAG_NAMES, Counts, Pos
 
 RATIO = 3.0  # EstimatedCompressionRatio default (bgzf/.../EstimatedCompressionRatio.scala)
 
@@ -143,29 +143,30 @@ class FullCheckParts:
     Counts, the first `limit` close calls of keys 1 and 2 as PosMetadata lines, and the comparison with the
     `.records` truth.  Parts of consecutive ranges merge in file order (merge_parts) — Spark's reduceByKey of Counts
     and the driver's take(limit) of the sampled positions (FullCheck.scala:141-191, CheckerApp.scala:140-222)."""
-    totals: np.ndarray      # (19,)
-    by_key: np.ndarray      # (21, 19): keys 1-2 exact (the report prints only those)
-    positions: np.ndarray   # (21,)
-    rbe: np.ndarray         # (21, 128) readsBeforeError by key
-    pair: np.ndarray        # (19, 19) close-call flag pairs
-    n_positions: int
+    counts: Counts          # by_key: keys 1-2 exact (the report prints only those)
     compressed: int
     close: dict             # key -> PosMetadata lines of the first `limit` positions with that key
     truth: Optional[dict]   # {"tp", "fp": [(F, PosMetadata line or None)], "fn": [Pos text]} with a .records file
 
+    def pack(self) -> np.ndarray:
+        """The part's summable words, int64[N_COUNT_WORDS + 1] (what the ranks all_reduce): Counts, then compressed."""
+        return np.append(self.counts.pack(), np.int64(self.compressed))
+
+    @staticmethod
+    def unpack(v: np.ndarray, close: dict, truth: Optional[dict]) -> "FullCheckParts":
+        return FullCheckParts(Counts.unpack(v[:-1]), int(v[-1]), close, truth)
+
 
 def merge_parts(parts: Sequence[FullCheckParts], limit: int) -> FullCheckParts:
     """Shards in file order → one report's parts (counts summed, sampled lines concatenated and cut to `limit`)."""
-    def add(name):
-        return sum(getattr(q, name) for q in parts)
     close = {k: [ln for q in parts for ln in q.close.get(k, [])][:limit] for k in (1, 2)}
     truth = None
     if parts and all(q.truth is not None for q in parts):
         fp = [x for q in parts for x in q.truth["fp"]]
         truth = {"tp": sum(q.truth["tp"] for q in parts), "fp": fp,
                  "fn": [x for q in parts for x in q.truth["fn"]]}
-    return FullCheckParts(add("totals"), add("by_key"), add("positions"), add("rbe"), add("pair"),
-                          add("n_positions"), add("compressed"), close, truth)
+    return FullCheckParts(sum((q.counts for q in parts), Counts.zero()), sum(q.compressed for q in parts), close,
+                          truth)
 
 
 def truth_lines(n_positions: int, compressed: int, tp: int, fps: Sequence[Tuple[int, Optional[str]]],
@@ -198,21 +199,21 @@ def truth_lines(n_positions: int, compressed: int, tp: int, fps: Sequence[Tuple[
 
 def full_check_lines(p: FullCheckParts, limit: int) -> List[str]:
     """FullCheck.scala:141-322 report text from (merged) parts."""
-    out = []
+    out, c = [], p.counts
     if p.truth is not None:
         fp, fn = p.truth["fp"], p.truth["fn"]
         if fp or fn:  # FullCheck.scala:108-114: a full-check call disagreeing with the records is an error
             raise RuntimeError(f"{len(fp)} false positives, {len(fn)} false negatives against the .records truth")
-        out += truth_lines(p.n_positions, p.compressed, p.truth["tp"], fp, fn, limit) + [""]
+        out += truth_lines(c.n_positions, p.compressed, p.truth["tp"], fp, fn, limit) + [""]
     field_names = FLAG_NAMES[:19]
 
     def pairs(vec):
         return [(field_names[i], int(vec[i])) for i in range(19)]
 
-    npos = p.positions
+    npos = c.positions
     if npos[1] > 0:  # critical (key-1) section, FullCheck.scala:230-258
         out.append("Critical error counts (true negatives where only one check failed):")
-        out += ["\t" + l for l in count_lines(pairs(p.by_key[1]), False, False)]
+        out += ["\t" + l for l in count_lines(pairs(c.by_key[1]), False, False)]
         out.append("")
         n1 = int(npos[1])
         print_limited(out, p.close[1], n1, f"{n1} critical positions:",
@@ -228,21 +229,21 @@ def full_check_lines(p: FullCheckParts, limit: int) -> List[str]:
         hist = []
         for i in range(19):
             for j in range(19):
-                if p.pair[i, j]:
-                    hist.append((int(p.pair[i, j]), (1 << i) | (1 << j)))
+                if c.pair_hist[i, j]:
+                    hist.append((int(c.pair_hist[i, j]), (1 << i) | (1 << j)))
         hist.sort(key=lambda t: -t[0])  # stable: reduceByKey output order is not pinned beyond the counts
         if hist and hist[0][0] > 1:
             print_limited(out, [f"{n}:\t{show_flags(F)}" for n, F in hist], None, "Histogram:",
                           lambda _: "Histogram:", limit, indent="\t")
             out.append("")
         out.append("\tPer-flag totals:")
-        out += ["\t\t" + l for l in count_lines(pairs(p.by_key[2]), False, False)]
+        out += ["\t\t" + l for l in count_lines(pairs(c.by_key[2]), False, False)]
         out.append("")
     else:
         out += ["No positions where exactly two checks failed", ""]
-    rb = [(k, int(p.rbe[:, k].sum())) for k in range(1, 128) if p.rbe[:, k].sum()]
+    rb = [(k, int(c.reads_before_error[:, k].sum())) for k in range(1, 128) if c.reads_before_error[:, k].sum()]
     out.append("Total error counts:")
-    out += ["\t" + l for l in count_lines(pairs(p.totals), True, True, rb)]
+    out += ["\t" + l for l in count_lines(pairs(c.totals), True, True, rb)]
     out.append("")
     return out
 
@@ -250,12 +251,13 @@ def full_check_lines(p: FullCheckParts, limit: int) -> List[str]:
 class FullCheckReport:
     """full-check over the blocks selected by `ranges` (None = whole file) of one context.  `blocks` (a block-index
     mask) restricts it further to the blocks a shard owns; `names` = the header's contig names (a shard's stream
-    does not start at the header)."""
+    does not start at the header).  `data` keeps its place in the signature for existing callers and is not kept: the
+    report reads everything through `f`, and a stored reference held the whole file's bytes alive."""
 
     def __init__(self, f: sbam.BamFile, data: Optional[bytes], records_path: Optional[str], limit: int = 10,
                  ranges: Optional[List[Tuple[int, int]]] = None, reads_to_check: int = 10,
                  blocks: Optional[np.ndarray] = None, names: Optional[List[str]] = None):
-        self.f, self.data, self.limit, self.R = f, data, limit, reads_to_check
+        self.f, self.limit, self.R = f, limit, reads_to_check
         st, cs, us, uo = f.blocks()
         sel = np.ones(st.size, bool) if ranges is None else \
             np.any([(st >= lo) & (st < hi) for lo, hi in ranges], axis=0)
@@ -370,27 +372,16 @@ class FullCheckReport:
     def parts(self) -> FullCheckParts:
         """The full checker over every position of the selected blocks (Counts by the bit-sliced counts path: keys
         1-2 per flag, positions per key, pairs, readsBeforeError, totals) plus the sampled close calls."""
-        by_key = np.zeros((21, 19), np.int64)
-        npos = np.zeros(21, np.int64)
-        totals = np.zeros(19, np.int64)
-        rbe = np.zeros((21, 128), np.int64)
-        pair = np.zeros((19, 19), np.int64)
-        n_positions = 0
-        calls_bits = []
+        counts, calls_bits = Counts.zero(), []
         has_truth = bool(self.records_path) and os.path.exists(self.records_path)
         for x0, x1 in self.runs:
             c, bits = self.f.check_full_counts(x0, x1, self.R, want_bitmap=True)
-            by_key += c.by_key
-            npos += c.positions
-            totals += c.totals
-            rbe += c.reads_before_error
-            pair += c.pair_hist
-            n_positions += x1 - x0
+            counts += c
             calls_bits.append((x0, bits))
-        close = {k: [self.pos_metadata(x, w) for x, w in self.close_calls(k, min(self.limit, int(npos[k])))]
+        close = {k: [self.pos_metadata(x, w) for x, w in self.close_calls(k, min(self.limit, int(counts.positions[k])))]
                  for k in (1, 2)}
         truth = self.truth_part(calls_bits) if has_truth else None
-        return FullCheckParts(totals, by_key, npos, rbe, pair, n_positions, self.compressed, close, truth)
+        return FullCheckParts(counts, self.compressed, close, truth)
 
     def lines(self) -> List[str]:
         return full_check_lines(self.parts(), self.limit)
@@ -686,6 +677,15 @@ def view_main(a) -> int:
     return 0
 
 
+def write_report(lines: Sequence[str], out: Optional[str]):
+    """The report text to the file `out`, or to stdout."""
+    text = "\n".join(lines) + "\n"
+    if out:
+        open(out, "w").write(text)
+    else:
+        sys.stdout.write(text)
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
     ap = argparse.ArgumentParser(prog="sbam.cli")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -725,11 +725,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             return spawn_ranks(a.gpus, sys.argv[1:] if argv is None else argv)
         lines = sharded_lines(a)
         if lines is not None:
-            text = "\n".join(lines) + "\n"
-            if a.out:
-                open(a.out, "w").write(text)
-            else:
-                sys.stdout.write(text)
+            write_report(lines, a.out)
         return 0
     dev = getattr(a, "device", None) or 0
     if a.cmd == "full-check" and a.windows == 0:
@@ -743,19 +739,15 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         from sbam import dist as sdist
         parts = sdist.full_check_file(a.bam, a.print_limit, a.intervals, a.reads_to_check, world=a.windows,
                                       device=dev, records_path=a.bam + ".records")
-        text = "\n".join(full_check_lines(parts, a.print_limit)) + "\n"
-        if a.out:
-            open(a.out, "w").write(text)
-        else:
-            sys.stdout.write(text)
+        write_report(full_check_lines(parts, a.print_limit), a.out)
         return 0
     data = open(a.bam, "rb").read()
     with sbam.BamFile(data, path=a.bam, device=dev) as f:
         if a.cmd == "full-check":
-            rep = FullCheckReport(f, data, a.bam + ".records", a.print_limit, a.intervals, a.reads_to_check)
+            rep = FullCheckReport(f, None, a.bam + ".records", a.print_limit, a.intervals, a.reads_to_check)
             lines = rep.lines()
         elif a.cmd == "check-bam":
-            rep = FullCheckReport(f, data, a.bam + ".records", a.print_limit, a.intervals, a.reads_to_check)
+            rep = FullCheckReport(f, None, a.bam + ".records", a.print_limit, a.intervals, a.reads_to_check)
             if not os.path.exists(rep.records_path):
                 raise SystemExit(f"check-bam -s needs the indexed records {rep.records_path} (index-records)")
             lines = rep.check_bam_lines()
@@ -774,11 +766,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             lines = compute_splits_lines(f, sbam.effective_split_size(a.max_split_size), a.print_limit)
         else:
             lines = count_reads_lines(f, sbam.effective_split_size(a.max_split_size))
-    text = "\n".join(lines) + "\n"
-    if a.out:
-        open(a.out, "w").write(text)
-    else:
-        sys.stdout.write(text)
+    write_report(lines, a.out)
     return 0
 
 

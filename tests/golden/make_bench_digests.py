@@ -3,7 +3,7 @@
 
 bench.py prints, for its full-check workload, two sharding-independent digests of the whole file's result:
 
-* ``counts``: sha1[:16] of the packed full-check Counts vector (sbam.dist.pack_counts: per-flag totals, keys 1-2
+* ``counts``: sha1[:16] of the packed full-check Counts vector (sbam.Counts.pack: per-flag totals, keys 1-2
   per flag, positions per key, readsBeforeError, close-call pairs, successes, TooFewFixedBlockBytes-only results,
   positions) — FullCheck.scala:141-191;
 * ``splits``: sha1[:16] of the split rows (first record Pos, non-empty, records per split) of compute-splits at

@@ -237,6 +237,34 @@ def test_full_check_parts_merge_in_file_order(golden, bam, args):
     assert "\n".join(cli.full_check_lines(merged, 10)) + "\n" == open(os.path.join(GOLDEN, "full-check", golden)).read()
 
 
+def test_full_check_parts_reduce_vector():
+    """What full_check_file all_reduces for one part: the packed Counts plus one word for the compressed size; it
+    unpacks to the part it came from (no process group needed), and the vectors of two parts add up to their merge."""
+    import numpy as np
+    import sbam
+    from sbam import cli
+    data = open(os.path.join(FIXTURES, "2.bam"), "rb").read()
+    ob = OracleBam(data)
+    nb = ob.blocks()[0].size
+    parts = []
+    for a, b in ((0, nb // 2), (nb // 2, nb)):
+        m = np.zeros(nb, bool)
+        m[a:b] = True
+        parts.append(cli.FullCheckReport(ob, None, os.path.join(FIXTURES, "2.bam.records"), 10, blocks=m).parts())
+    for p in parts:
+        v = p.pack()
+        assert v.dtype == np.int64 and v.shape == (sbam.N_COUNT_WORDS + 1,)
+        assert np.array_equal(v[:-1], p.counts.pack()) and v[-1] == p.compressed > 0
+        q = cli.FullCheckParts.unpack(v, p.close, p.truth)
+        assert np.array_equal(q.counts.pack(), p.counts.pack()) and q.compressed == p.compressed
+        assert q.counts.n_positions == p.counts.n_positions > 0 and q.counts.n_success == p.counts.n_success
+        assert q.close is p.close and q.truth is p.truth
+        assert cli.full_check_lines(cli.merge_parts([q], 10), 10) == cli.full_check_lines(cli.merge_parts([p], 10), 10)
+    merged = cli.merge_parts(parts, 10)
+    assert np.array_equal(merged.pack(), parts[0].pack() + parts[1].pack())
+    assert merged.counts.n_success == 2500
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("golden,bam,args", [CASES[0], CASES[4], CASES[5]])
 @pytest.mark.parametrize("mode", [["--gpus", "2", "--dist-backend", "gloo", "--device", "0"], ["--windows", "3"]])

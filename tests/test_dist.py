@@ -291,59 +291,57 @@ def test_rccl_collectives_single_rank(tmp_path):
     assert golden_ok
 
 
-def test_hbm_budget_and_auto_windows():
-    """HBM per compressed byte (DESIGN.md §Data layout) from the file's measured BGZF ratio; a range that starts
-    inside a block finds the first header; auto_windows fits two contexts in 80 % of the free bytes."""
+def _random_counts(rng):
+    import sbam
+    shapes = ((19,), (21, 19), (21,), (21, 128), (19, 19))
+    a = [rng.integers(-(1 << 62), 1 << 62, shape, dtype=np.int64) for shape in shapes]
+    return sbam.Counts(*a, *(int(x) for x in rng.integers(0, 1 << 40, 3)))
+
+
+def test_counts_pack_layout():
+    """The packed Counts vector (what ranks all_reduce and tests/golden/bench_digests.json pins): totals at 0, by_key at
+    19, positions at 418, reads_before_error at 439, pair_hist at 3127, then n_success, n_too_few_fixed, n_positions;
+    unpack gives every field back, + is field-wise, and unpack_counts is the dict bench.py indexes."""
+    import sbam
     from sbam import dist as sdist
-    src, size = sdist.file_source(os.path.join(FIXTURES, "2.bam"))
-    r = sdist.bgzf_ratio(src, size)
-    assert 2.9 < r < 3.2
-    assert abs(sdist.bgzf_ratio(lambda lo, hi: src(lo + 1000, hi + 1000), size - 1000) - r) < 0.05
-    per = sdist.hbm_bytes_per_compressed_byte(1.1 * r)
-    assert abs(per - (1 + 1.1 * r * 2.1875 + 0.05)) < 1e-9
-    assert sdist.bgzf_sample_stats(src, size)[1] < 0.05  # zlib-6 BAM blocks: the arena's default share
-    need = size * per * 2
-    assert sdist.auto_windows(size, src, int(need / 0.8) + 1) == 1
-    assert sdist.auto_windows(size, src, int(need / 0.8 / 3) + 1) == 3
+    rng = np.random.default_rng(11)
+    c, d = _random_counts(rng), _random_counts(rng)
+    v = c.pack()
+    want = np.concatenate([c.totals, c.by_key.ravel(), c.positions, c.reads_before_error.ravel(), c.pair_hist.ravel(),
+                           np.array([c.n_success, c.n_too_few_fixed, c.n_positions], np.int64)])
+    assert v.dtype == np.int64 and v.tobytes() == want.astype(np.int64).tobytes()
+    assert v.size == sdist.N_COUNT_WORDS == sbam.N_COUNT_WORDS == 3491
+    for name, off in (("totals", 0), ("by_key", 19), ("positions", 418), ("reads_before_error", 439),
+                      ("pair_hist", 3127)):
+        a = getattr(c, name)
+        assert np.array_equal(v[off:off + a.size], a.ravel())
+    assert v[3488:].tolist() == [c.n_success, c.n_too_few_fixed, c.n_positions]
+    assert np.array_equal(sdist.pack_counts(c), v)
+    back = sbam.Counts.unpack(v)
+    u = sdist.unpack_counts(v)
+    assert isinstance(u, dict) and set(u) == {"totals", "by_key", "positions", "reads_before_error", "pair_hist",
+                                              "n_success", "n_too_few_fixed", "n_positions"}
+    for name in u:
+        assert np.array_equal(getattr(back, name), getattr(c, name)) and np.array_equal(u[name], getattr(c, name))
+        assert np.shape(u[name]) == np.shape(getattr(c, name))
+    assert type(u["n_success"]) is int and type(back.n_positions) is int
+    assert np.array_equal((c + d).pack(), c.pack() + d.pack())
+    assert not sbam.Counts.zero().pack().any()
+    assert np.array_equal(sum([c, d, c], sbam.Counts.zero()).pack(), 2 * c.pack() + d.pack())
 
 
-def _bgzf_block(payload: bytes, level: int, strategy: int = 0) -> bytes:
-    """One BGZF block (RFC 1952 member with the BC extra field) of `payload`, raw-deflated at `level`."""
-    import struct
-    import zlib
-    co = zlib.compressobj(level, zlib.DEFLATED, -15, 9, strategy)
-    data = co.compress(payload) + co.flush()
-    bsize = 18 + len(data) + 8 - 1
-    hdr = b"\x1f\x8b\x08\x04" + b"\x00" * 4 + b"\x00\xff" + struct.pack("<HBBHH", 6, 66, 67, 2, bsize)
-    return hdr + data + struct.pack("<II", zlib.crc32(payload), len(payload))
-
-
-def test_auto_windows_budgets_arena_for_stored_blocks():
-    """stored and Huffman-only blocks need 2 B of token arena per uncompressed byte, so auto_windows
-    budgets them (bgzf_sample_stats' low-ratio share) instead of the 1/16 default, and picks more windows than the
-    same ratio at the default would."""
-    import zlib
+def test_split_planners_agree():
+    """sbam.hadoop_splits (sbam_file_splits in libsbam.so: no context, no GPU) and the pure-Python dist.hadoop_splits,
+    which plans shards without the library, give the same FileInputFormat splits — random sizes and the edges of the
+    1.1 slop."""
+    import sbam
     from sbam import dist as sdist
-    rng = np.random.default_rng(5)
-    raw = rng.integers(0, 4, 60000, dtype=np.uint8).tobytes()
-    stored = b"".join(_bgzf_block(raw, 0) for _ in range(40))
-    huff = b"".join(_bgzf_block(raw, 6, zlib.Z_HUFFMAN_ONLY) for _ in range(40))
-    for blob in (stored, huff):
-        buf = np.frombuffer(blob, np.uint8)
-        src = (lambda b: lambda lo, hi: b[lo:hi])(buf)
-        r, frac = sdist.bgzf_sample_stats(src, buf.size)
-        assert frac == 1.0
-        per = sdist.hbm_bytes_per_compressed_byte(1.1 * r, frac)
-        assert per > sdist.hbm_bytes_per_compressed_byte(1.1 * r) + 2.0 * 1.1 * r
-        free = int(buf.size * per * 2 / 0.8 / 2) + 1  # room for half of what the worst case needs
-        assert sdist.auto_windows(buf.size, src, free) == 2
-    # the token counter: one token per byte for stored and Huffman-only streams; zlib-6 matches take two tokens each
-    import zlib as z
-    for level, strat in ((0, 0), (6, z.Z_HUFFMAN_ONLY)):
-        co = z.compressobj(level, z.DEFLATED, -15, 9, strat)
-        assert sdist.deflate_token_count(co.compress(raw) + co.flush()) == len(raw)
-    text = b"".join(b"read%07d\tACGTTGCA\n" % i for i in range(3000))
-    co = z.compressobj(6, z.DEFLATED, -15, 8, 0)
-    t = sdist.deflate_token_count(co.compress(text) + co.flush())
-    assert 0 < t < len(text) // 2 and t % 1 == 0
-    assert sdist.deflate_token_count(b"\xff\xff\xff") == -1  # block type 3
+    rng = np.random.default_rng(7)
+    cases = [(0, 5), (5, 5), (11, 10), (12, 10)]
+    cases += [(int(1.1 * s) + d, s) for s in (3, 1000, 1 << 20) for d in (-1, 0, 1)]
+    # random pairs; a split no smaller than 1/4096 of the file keeps each list short
+    for _ in range(300):
+        f = int(rng.integers(0, (1 << 34) + 1))
+        cases.append((f, int(rng.integers(max(1, f >> 12), (1 << 26) + 1))))
+    for f, s in cases:
+        assert sbam.hadoop_splits(f, s) == sdist.hadoop_splits(f, s), (f, s)

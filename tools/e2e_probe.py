@@ -61,7 +61,7 @@ def main():
     ser = []
     for w in range(W):
         t0 = time.perf_counter()
-        sh = pipe._load(w, 0)
+        sh = pipe._load(w, pipe.stager.submit(pipe._stage, w))
         t1 = time.perf_counter()
         sh.step()
         t2 = time.perf_counter()

@@ -10,7 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "tools"), os.path.join(ROOT, "spark-bam_amd")]
 import numpy as np
 import synth
-from sbam.dist import _CL_ORDER, _LEN_EXTRA, _DIST_EXTRA
+from sbam.bgzf_sample import _CL_ORDER, _LEN_EXTRA, _DIST_EXTRA
 
 def huff(lengths):
     tab = [0] * 32768

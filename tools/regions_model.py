@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "spark-bam_amd"), os.path.join(ROOT, "tools")]
 from pair_stats import huff  # noqa: E402
 from regions_debug import dblocks, LBASE  # noqa: E402
-from sbam.dist import _CL_ORDER, _LEN_EXTRA, _DIST_EXTRA  # noqa: E402
+from sbam.bgzf_sample import _CL_ORDER, _LEN_EXTRA, _DIST_EXTRA  # noqa: E402
 
 KRS, KRW, KH, KCP, KCPS = 480, 480, 48, 12, 8
 LIT, LEN, DIST, SPEC = 0, 1, 2, 3

@@ -12,7 +12,7 @@ sys.path[:0] = [os.path.join(ROOT, "tools"), os.path.join(ROOT, "spark-bam_amd")
 import numpy as np  # noqa: E402
 import synth  # noqa: E402
 from pair_stats import huff  # noqa: E402
-from sbam.dist import _CL_ORDER, _LEN_EXTRA, _DIST_EXTRA  # noqa: E402
+from sbam.bgzf_sample import _CL_ORDER, _LEN_EXTRA, _DIST_EXTRA  # noqa: E402
 
 def dblocks(payload):
     """(final, header_start_bit, data_start_bit, end_bit, nsym) per deflate block"""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Experiment: host wall time of each phase of one bench step (sbam/dist.py GpuShard._once + shard_pass), to
+"""Experiment: host wall time of each phase of one bench step (sbam/dist.py GpuShard.run + shard_pass), to
 find time outside the kernels.  Prints one JSON line of median ms per phase."""
 import argparse
 import json
