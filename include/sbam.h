@@ -33,7 +33,8 @@ extern "C" {
 #define SBAM_ERR_HIP 7            /* HIP runtime failure (device, allocation, launch)                       */
 #define SBAM_ERR_STATE 8          /* stage called out of order (e.g. check before inflate)                  */
 #define SBAM_ERR_HALO 9           /* a check needed bytes past a shard's loaded range (grow the halo)       */
-#define SBAM_ERR_RECORD 10        /* variable-length fields overrun block_size; error.position = record offset */
+#define SBAM_ERR_RECORD 10        /* variable-length fields overrun block_size, or (sbam_build_index) a record no
+                                     BAI can index; error.position = record offset                          */
 
 typedef struct sbam_ctx sbam_ctx;
 
@@ -298,10 +299,78 @@ int sbam_get_record_fields(sbam_ctx *ctx, const sbam_record_fields *out);
  * that was not selected is NULL. */
 int sbam_record_fields_device(sbam_ctx *ctx, sbam_record_fields *dev, int64_t *i0, int64_t *n);
 
+/* ---- BAI index writer (SAM spec §5.2, §5.3; the layout the reference reads in check/.../bam/index/Index.scala:53-90) -- */
+
+/* The index is built from the record columns of the last sbam_load_records, in file order, by these rules (the usual
+ * samtools/htslib writer's; pinned by the reference's 2.bam.bai and 5k.bam.bai):
+ *   span    beg = max(pos, 0); end = pos + the CIGAR's reference length (M, D, N, =, X) for a mapped record (flag 4
+ *           clear) with a positive one, else beg + 1; bin = reg2bin(beg, end) (14-bit minimum shift, 5 levels),
+ *           computed, never the record's own bin field;
+ *   run     a maximal stretch of consecutive records with ref_id >= 0 and the same (ref_id, bin): one chunk
+ *           [virtual offset of its first record, virtual offset behind its last); a record with ref_id < 0 breaks a run;
+ *   linear  ioffset[ref][w] = the smallest record start over the records touching 16 kb window w; an untouched window
+ *           takes the next touched one's value (filled from the end);
+ *   meta    per reference: smallest start, largest end, mapped and unmapped (flag 4) records; n_no_coor = records with
+ *           ref_id < 0; n_unsorted = records whose ((uint32) ref_id, pos) is below their predecessor's.
+ * The .bai bytes list a reference's bins in ascending bin number, the metadata pseudo-bin 37450 last (a reader must
+ * not rely on an order: the reference's fixtures list theirs in hash-table order). */
+typedef struct {
+  int32_t n_ref;
+  int32_t reserved;
+  int64_t n_runs;        /* entries of sbam_get_index_runs */
+  int64_t n_intv_total;  /* entries of sbam_get_index_refs' ioffset */
+  int64_t n_no_coor;
+  int64_t n_unsorted;
+  int64_t n_records;
+} sbam_index_totals;
+
+/* Build the index of the whole file on the GPU (SAM spec §5.2; reader: check/.../bam/index/Index.scala:53-90).  Needs a
+ * whole-file context (base_offset 0, file_size == len), known contig lengths, and a preceding sbam_load_records over
+ * every split (first = 0 through the last; a file that ends behind its header needs none); else SBAM_ERR_STATE.
+ * A record with ref_id >= n_ref, a reference end past 2^29, or CIGAR ops past its block_size or the stream end is
+ * SBAM_ERR_RECORD with error.position = the stream offset of the first such record; nothing is produced.  The results
+ * live on the device, owned by ctx (grow-only buffers sized by one rule; sbam_reserve serves streamed windows and does
+ * not size them), until the next load, reset or close. */
+int sbam_build_index(sbam_ctx *ctx, sbam_index_totals *totals);
+
+/* The raw runs of the last sbam_build_index in file order, n_runs entries each (SAM spec §5.2 chunks before binning;
+ * Index.scala:53-57 Chunk).  A NULL member is not copied. */
+int sbam_get_index_runs(sbam_ctx *ctx, int32_t *ref, uint32_t *bin, uint64_t *beg, uint64_t *end);
+
+/* The linear index after the fill and the per-reference metadata of the last sbam_build_index (SAM spec §5.2 ioffset
+ * and the pseudo-bin 37450; Index.scala:60-90): intv_off has n_ref + 1 entries, reference r's windows are
+ * ioffset[intv_off[r] .. intv_off[r + 1]); the other members have n_ref entries (off_beg of a reference without records
+ * is UINT64_MAX).  A NULL member is not copied. */
+int sbam_get_index_refs(sbam_ctx *ctx, int64_t *intv_off, uint64_t *ioffset, uint64_t *off_beg, uint64_t *off_end,
+                        int64_t *n_mapped, int64_t *n_unmapped);
+
+/* Runs, linear index and metadata -> .bai bytes (SAM spec §5.2; what Index.scala:60-90 parses).  Host only: no context,
+ * no device.  Per reference: group the runs by bin in file order; for level 5 down to 1, every present bin in ascending
+ * number (below level 5 its chunks sorted first) whose (last chunk's end >> 16) - (first chunk's beg >> 16) < 0x10000
+ * and whose parent (bin - 1) >> 3 exists is appended to the parent and deleted; bin 0 is sorted; every bin's chunks are
+ * coalesced in order (c joins the kept chunk m when m.end >> 16 >= c.beg >> 16); pseudo-bin 37450 holds
+ * (off_beg, off_end) and (n_mapped, n_unmapped).  A reference with no records has n_bin = 0 and n_intv = 0.  ioffset
+ * entries equal to UINT64_MAX count as untouched and are filled from the end.  *n_bytes receives the size; when cap is
+ * smaller nothing is written and the result is SBAM_ERR_ARG. */
+int sbam_bai_assemble(int32_t n_ref, int64_t n_runs, const int32_t *run_ref, const uint32_t *run_bin,
+                      const uint64_t *run_beg, const uint64_t *run_end, const int64_t *intv_off,
+                      const uint64_t *ioffset, const uint64_t *off_beg, const uint64_t *off_end,
+                      const int64_t *n_mapped, const int64_t *n_unmapped, int64_t n_no_coor, uint8_t *out, int64_t cap,
+                      int64_t *n_bytes);
+
+/* sbam_bai_assemble over the last sbam_build_index (SAM spec §5.2; Index.scala:60-90 reads these bytes back): the file
+ * a JVM caller stores beside the BAM as <name>.bam.bai.  cap too small: SBAM_ERR_ARG, *n_bytes = the size needed. */
+int sbam_write_bai(sbam_ctx *ctx, uint8_t *out, int64_t cap, int64_t *n_bytes);
+
+/* CIGAR ops above which sbam_build_index sums a record's reference length with a whole wave (SAM spec §4.2 n_cigar_op;
+ * no reference counterpart, Index.scala:53-90 only reads): for tests that must reach that path. */
+int sbam_index_long_cigar_ops(void);
+
 /* ---- timing support for bench/profiling -------------------------------------------------------- */
 /* Device time (ms, HIP events on the library's stream) of the most recent launch of a named kernel
  * family: "scan", "inflate", "check_full", "check_eager", "records", "load_records", "record_fields" (the gather of
- * sbam_load_record_fields; "record_field_sizes": its sizes and scan). Returns -1 if none. */
+ * sbam_load_record_fields; "record_field_sizes": its sizes and scan), "index" (sbam_build_index, from its first pass
+ * through the linear index's fill). Returns -1 if none. */
 double sbam_last_kernel_ms(sbam_ctx *ctx, const char *kernel);
 
 #ifdef __cplusplus

@@ -218,6 +218,7 @@ struct sbam_ctx {
   DevBuf<int64_t> d_lens;
   std::vector<int64_t> h_lens;
   sbam_pos header_end{0, 0, 0};
+  int64_t header_x = -1;  // stream offset of header_end (-1: the lengths came from sbam_set_contig_lengths)
   // success bitmap of the latest full/eager check, and what it covers (set_bitmap / drop_bitmap)
   DevBuf<unsigned long long> d_bitmap;
   int64_t bm_x0 = 0, bm_x1 = 0;
@@ -243,6 +244,19 @@ struct sbam_ctx {
   sbam_record_fields fdev{};  // device pointers (data of unselected fields: null)
   int64_t f_i0 = 0, f_n = -1;
   sbam_record_field_totals f_tot{};
+  // sbam_load_records covered every split of a whole file (what sbam_build_index needs)
+  bool loaded_all = false;
+  // BAI index of the last sbam_build_index: per-record scratch (end, bin), per-workgroup run heads, the counter
+  // words (4 scalars + 5 per reference), the runs (ref, bin | beg | end) and the linear index with its offsets
+  DevBuf<int32_t> d_iend;
+  DevBuf<uint32_t> d_ibin;
+  DevBuf<int64_t> d_iheads, d_iintv;
+  DevBuf<unsigned long long> d_istat, d_irun, d_ioff;
+  DevBuf<int32_t> d_irunref;
+  DevBuf<uint32_t> d_irunbin;
+  bool idx_built = false;
+  sbam_index_totals idx_tot{};
+  std::vector<int64_t> idx_intv;  // n_ref + 1 window offsets
   // small device scratch
   DevBuf<int64_t> d_small;  // 64 int64
   DevBuf<unsigned long long> d_counts;
@@ -315,6 +329,7 @@ hipError_t drop_stages(sbam_ctx *c) {
   drop_bitmap(c);
   c->n_loaded = -1;
   c->f_n = -1;
+  c->loaded_all = c->idx_built = false;
   return e;
 }
 
@@ -374,6 +389,13 @@ hipError_t ensure_record_columns(sbam_ctx *c, size_t N, bool *grew = nullptr, Re
   auto qu = [&](int j) { return reinterpret_cast<uint32_t *>(q(j)); };
   *cols = RecordColumnsDev{reinterpret_cast<int64_t *>(p), q(0), q(1), q(2), q(3), qu(4), qu(5), q(6), q(7), q(8), q(9)};
   return hipSuccess;
+}
+
+// the index's per-record scratch and run heads for N records
+hipError_t ensure_index(sbam_ctx *c, size_t N, bool *grew = nullptr) {
+  HIPTRY(c->d_iend.ensure(N, grew));
+  HIPTRY(c->d_ibin.ensure(N, grew));
+  return c->d_iheads.ensure((size_t)index_blocks((int64_t)N) + 1, grew);
 }
 
 // Header.make details at relative offset q (for HeaderParseException).
@@ -834,6 +856,7 @@ int sbam_set_contig_lengths(sbam_ctx *c, int32_t n_ref, const int64_t *lengths) 
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->h_lens.assign(lengths, lengths + n_ref);
   c->nref = n_ref;
+  c->header_x = -1;
   drop_bitmap(c);
   return SBAM_OK;
 }
@@ -867,6 +890,7 @@ int sbam_header(sbam_ctx *c, int32_t *n_ref, int64_t *lengths, int32_t cap, sbam
   int rc = sbam_set_contig_lengths(c, nr, lens.data());
   if (rc) return rc;
   c->header_end = pos_of(c, x);
+  c->header_x = x;
   if (n_ref) *n_ref = nr;
   if (lengths)
     for (int32_t i = 0; i < nr && i < cap; i++) lengths[i] = lens[i];
@@ -1280,6 +1304,7 @@ int sbam_load_records(sbam_ctx *c, const sbam_split_args *a, int64_t first, int6
   HIPCHK(c, hipSetDevice(c->device));
   c->n_loaded = -1;
   c->f_n = -1;
+  c->loaded_all = c->idx_built = false;
   std::vector<int64_t> xs, xe, cnt;
   rc = split_starts(c, a, first, count, xs, xe);
   if (rc) return rc;
@@ -1304,6 +1329,11 @@ int sbam_load_records(sbam_ctx *c, const sbam_split_args *a, int64_t first, int6
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->n_loaded = N;
+  {
+    int64_t ns = 0;
+    sbam_file_splits(c->file_size, a->split_size, nullptr, nullptr, 0, &ns);
+    c->loaded_all = c->base == 0 && c->file_size == c->D && first == 0 && count == ns;
+  }
   if (split_counts_out)
     for (int64_t i = 0; i < count; i++) split_counts_out[i] = cnt[i];
   if (n_records) *n_records = N;
@@ -1455,6 +1485,215 @@ int sbam_record_fields_device(sbam_ctx *c, sbam_record_fields *d, int64_t *i0, i
   *d = c->fdev;
   if (i0) *i0 = c->f_i0;
   if (n) *n = c->f_n;
+  return SBAM_OK;
+}
+
+// ---- BAI index writer (SAM spec §5.2, §5.3; read back by check/.../bam/index/Index.scala:53-90) ------------------
+int sbam_index_long_cigar_ops(void) { return index_long_cigar_ops(); }
+
+int sbam_build_index(sbam_ctx *c, sbam_index_totals *totals) {
+  if (!c) return SBAM_ERR_ARG;
+  if (c->base != 0 || c->file_size != c->D)
+    return set_err(c, SBAM_ERR_STATE, "sbam_build_index needs a whole-file context");
+  // (a file that ends behind its header has no record for sbam_load_records to find: its index needs no load)
+  const bool no_records = c->L >= 0 && c->nref >= 0 && c->header_x == c->L;
+  if (c->L < 0 || c->nref < 0 || (!no_records && (c->n_loaded < 0 || !c->loaded_all)))
+    return set_err(c, SBAM_ERR_STATE, "sbam_build_index needs sbam_load_records over every split of the file");
+  if (int rc = ensure_blocks(c)) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->idx_built = false;
+  const int64_t N = no_records ? 0 : c->n_loaded;
+  const int32_t nref = c->nref;
+  HIPCHK(c, ensure_index(c, (size_t)N));
+  const size_t nstat = 4 + 5 * (size_t)nref;
+  HIPCHK(c, c->d_istat.ensure(nstat));
+  HIPCHK(c, c->d_iintv.ensure((size_t)nref + 1));
+  unsigned long long *w = c->d_istat;
+  const IndexStats st{w, w + 4, w + 4 + nref, w + 4 + 2 * (size_t)nref, w + 4 + 3 * (size_t)nref, w + 4 + 4 * (size_t)nref};
+  const RecordColumnsDev &k = c->rcols;
+  const IndexArgs ia{c->d_u,  c->L,        c->d_roff, k.block_pos, k.block_off, k.block_size, k.ref_id,
+                     k.pos,   k.bin_mq_nl, k.flag_nc, N,           nref,        c->d_bstart,  c->d_buoff,
+                     c->d_bc, c->d_bu,     c->blk.n,  c->base,     c->d_iend,   c->d_ibin};
+  std::vector<unsigned long long> hs(nstat, 0);
+  {
+    Timer t(c, "index");
+    HIPCHK(c, hipMemsetAsync(w, 0, nstat * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(w, 0xff, 8, c->stream));
+    if (nref) HIPCHK(c, hipMemsetAsync(st.off_beg, 0xff, (size_t)nref * 8, c->stream));
+    HIPCHK(c, launch_index_pass1(ia, st, c->d_iheads, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hs.data(), w, nstat * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (hs[0] != ~0ull) {
+      c->err.position = (int64_t)hs[0];
+      return set_err(c, SBAM_ERR_RECORD, "record at %lld: ref_id, reference end or CIGAR outside what a BAI can index",
+                     (long long)hs[0]);
+    }
+    const int64_t n_runs = (int64_t)hs[3];
+    c->idx_intv.assign((size_t)nref + 1, 0);
+    for (int32_t r = 0; r < nref; r++) c->idx_intv[r + 1] = c->idx_intv[r] + (int64_t)hs[4 + 4 * (size_t)nref + r];
+    const int64_t n_intv = c->idx_intv[nref];
+    HIPCHK(c, c->d_irunref.ensure((size_t)n_runs));
+    HIPCHK(c, c->d_irunbin.ensure((size_t)n_runs));
+    HIPCHK(c, c->d_irun.ensure(2 * (size_t)n_runs));
+    HIPCHK(c, c->d_ioff.ensure((size_t)n_intv));
+    HIPCHK(c, hipMemcpyAsync(c->d_iintv, c->idx_intv.data(), ((size_t)nref + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (n_intv) HIPCHK(c, hipMemsetAsync(c->d_ioff, 0xff, (size_t)n_intv * 8, c->stream));
+    const IndexRuns runs{c->d_irunref, c->d_irunbin, c->d_irun, c->d_irun + n_runs, n_runs};
+    HIPCHK(c, launch_index_pass2(ia, c->d_iheads, runs, c->d_iintv, c->d_ioff, c->stream));
+    c->idx_tot = sbam_index_totals{nref, 0, n_runs, n_intv, (int64_t)hs[1], (int64_t)hs[2], N};
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->idx_built = true;
+  if (totals) *totals = c->idx_tot;
+  return SBAM_OK;
+}
+
+int sbam_get_index_runs(sbam_ctx *c, int32_t *ref, uint32_t *bin, uint64_t *beg, uint64_t *end) {
+  if (!c) return SBAM_ERR_ARG;
+  if (!c->idx_built) return set_err(c, SBAM_ERR_STATE, "sbam_build_index has not run");
+  const size_t n = (size_t)c->idx_tot.n_runs;
+  if (!n) return SBAM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (ref) HIPCHK(c, hipMemcpyAsync(ref, c->d_irunref, n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (bin) HIPCHK(c, hipMemcpyAsync(bin, c->d_irunbin, n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (beg) HIPCHK(c, hipMemcpyAsync(beg, c->d_irun, n * 8, hipMemcpyDeviceToHost, c->stream));
+  if (end) HIPCHK(c, hipMemcpyAsync(end, c->d_irun + n, n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SBAM_OK;
+}
+
+int sbam_get_index_refs(sbam_ctx *c, int64_t *intv_off, uint64_t *ioffset, uint64_t *off_beg, uint64_t *off_end,
+                        int64_t *n_mapped, int64_t *n_unmapped) {
+  if (!c) return SBAM_ERR_ARG;
+  if (!c->idx_built) return set_err(c, SBAM_ERR_STATE, "sbam_build_index has not run");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t nref = (size_t)c->idx_tot.n_ref, nb = nref * 8;
+  if (intv_off) std::copy(c->idx_intv.begin(), c->idx_intv.end(), intv_off);
+  const unsigned long long *w = c->d_istat.get() + 4;
+  if (ioffset && c->idx_tot.n_intv_total)
+    HIPCHK(c, hipMemcpyAsync(ioffset, c->d_ioff, (size_t)c->idx_tot.n_intv_total * 8, hipMemcpyDeviceToHost, c->stream));
+  if (nref) {
+    if (n_mapped) HIPCHK(c, hipMemcpyAsync(n_mapped, w, nb, hipMemcpyDeviceToHost, c->stream));
+    if (n_unmapped) HIPCHK(c, hipMemcpyAsync(n_unmapped, w + nref, nb, hipMemcpyDeviceToHost, c->stream));
+    if (off_beg) HIPCHK(c, hipMemcpyAsync(off_beg, w + 2 * nref, nb, hipMemcpyDeviceToHost, c->stream));
+    if (off_end) HIPCHK(c, hipMemcpyAsync(off_end, w + 3 * nref, nb, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SBAM_OK;
+}
+
+int sbam_bai_assemble(int32_t n_ref, int64_t n_runs, const int32_t *run_ref, const uint32_t *run_bin,
+                      const uint64_t *run_beg, const uint64_t *run_end, const int64_t *intv_off,
+                      const uint64_t *ioffset, const uint64_t *off_beg, const uint64_t *off_end,
+                      const int64_t *n_mapped, const int64_t *n_unmapped, int64_t n_no_coor, uint8_t *out, int64_t cap,
+                      int64_t *n_bytes) {
+  constexpr uint32_t kMetaBin = 37450, kMaxBin = 37449;
+  if (n_ref < 0 || n_runs < 0 || !n_bytes || cap < 0 || (cap && !out)) return SBAM_ERR_ARG;
+  if (n_runs && (!run_ref || !run_bin || !run_beg || !run_end)) return SBAM_ERR_ARG;
+  if (n_ref && (!intv_off || !off_beg || !off_end || !n_mapped || !n_unmapped)) return SBAM_ERR_ARG;
+  typedef std::pair<uint64_t, uint64_t> Chunk;  // (beg, end): sorts by beg, then end
+  std::vector<std::map<uint32_t, std::vector<Chunk>>> bins((size_t)n_ref);
+  for (int64_t k = 0; k < n_runs; k++) {  // 1. the runs by bin, in file order
+    if (run_ref[k] < 0 || run_ref[k] >= n_ref || run_bin[k] >= kMaxBin) return SBAM_ERR_ARG;
+    bins[run_ref[k]][run_bin[k]].push_back(Chunk(run_beg[k], run_end[k]));
+  }
+  for (int32_t r = 0; r < n_ref; r++) {
+    if (intv_off[r + 1] < intv_off[r] || (intv_off[r + 1] > intv_off[r] && !ioffset)) return SBAM_ERR_ARG;
+    auto &B = bins[r];
+    for (int l = 5; l >= 1; l--) {  // 2. small bins move into their parents, leaves first
+      const uint32_t lo = ((1u << (3 * l)) - 1) / 7, hi = ((1u << (3 * l + 3)) - 1) / 7;
+      std::vector<uint32_t> present;
+      for (auto it = B.lower_bound(lo); it != B.end() && it->first < hi; ++it) present.push_back(it->first);
+      for (uint32_t b : present) {
+        std::vector<Chunk> &cs = B[b];
+        if (l < 5) std::sort(cs.begin(), cs.end());
+        auto parent = B.find((b - 1) >> 3);
+        if ((cs.back().second >> 16) - (cs.front().first >> 16) < 0x10000 && parent != B.end()) {
+          parent->second.insert(parent->second.end(), cs.begin(), cs.end());
+          B.erase(b);
+        }
+      }
+    }
+    auto b0 = B.find(0);  // 3.
+    if (b0 != B.end()) std::sort(b0->second.begin(), b0->second.end());
+    for (auto &kv : B) {  // 4. coalesce in order
+      std::vector<Chunk> &cs = kv.second;
+      size_t m = 0;
+      for (size_t k = 1; k < cs.size(); k++) {
+        if ((cs[m].second >> 16) >= (cs[k].first >> 16)) cs[m].second = std::max(cs[m].second, cs[k].second);
+        else cs[++m] = cs[k];
+      }
+      cs.resize(m + 1);
+    }
+  }
+  // the size, then the bytes
+  int64_t need = 8 + 8;
+  for (int32_t r = 0; r < n_ref; r++) {
+    need += 8;  // n_bin, n_intv
+    if (n_mapped[r] + n_unmapped[r] == 0 && bins[r].empty()) continue;
+    for (auto &kv : bins[r]) need += 8 + 16 * (int64_t)kv.second.size();
+    need += 8 + 32 + 8 * (intv_off[r + 1] - intv_off[r]);
+  }
+  *n_bytes = need;
+  if (cap < need) return SBAM_ERR_ARG;
+  uint8_t *p = out;
+  auto put32 = [&](uint32_t v) { std::memcpy(p, &v, 4); p += 4; };
+  auto put64 = [&](uint64_t v) { std::memcpy(p, &v, 8); p += 8; };
+  std::memcpy(p, "BAI\1", 4);
+  p += 4;
+  put32((uint32_t)n_ref);
+  for (int32_t r = 0; r < n_ref; r++) {
+    if (n_mapped[r] + n_unmapped[r] == 0 && bins[r].empty()) {
+      put32(0);
+      put32(0);
+      continue;
+    }
+    put32((uint32_t)bins[r].size() + 1);
+    for (auto &kv : bins[r]) {  // ascending bin number
+      put32(kv.first);
+      put32((uint32_t)kv.second.size());
+      for (const Chunk &ch : kv.second) {
+        put64(ch.first);
+        put64(ch.second);
+      }
+    }
+    put32(kMetaBin);  // 5. the metadata pseudo-bin, last
+    put32(2);
+    put64(off_beg[r]);
+    put64(off_end[r]);
+    put64((uint64_t)n_mapped[r]);
+    put64((uint64_t)n_unmapped[r]);
+    const int64_t ni = intv_off[r + 1] - intv_off[r];
+    put32((uint32_t)ni);
+    uint8_t *io = p;
+    uint64_t next = ~0ull;  // an untouched window takes the next touched one's value
+    for (int64_t wdw = ni - 1; wdw >= 0; wdw--) {
+      const uint64_t v = ioffset[intv_off[r] + wdw];
+      if (v != ~0ull) next = v;
+      std::memcpy(io + 8 * wdw, &next, 8);
+    }
+    p += 8 * ni;
+  }
+  put64((uint64_t)n_no_coor);
+  return SBAM_OK;
+}
+
+int sbam_write_bai(sbam_ctx *c, uint8_t *out, int64_t cap, int64_t *n_bytes) {
+  if (!c || !n_bytes || cap < 0 || (cap && !out)) return SBAM_ERR_ARG;
+  if (!c->idx_built) return set_err(c, SBAM_ERR_STATE, "sbam_build_index has not run");
+  const sbam_index_totals &t = c->idx_tot;
+  std::vector<int32_t> ref((size_t)t.n_runs);
+  std::vector<uint32_t> bin((size_t)t.n_runs);
+  std::vector<uint64_t> beg((size_t)t.n_runs), end((size_t)t.n_runs), ioff((size_t)t.n_intv_total);
+  const size_t nr = (size_t)t.n_ref;
+  std::vector<uint64_t> ob(nr), oe(nr);
+  std::vector<int64_t> nm(nr), nu(nr);
+  if (int rc = sbam_get_index_runs(c, ref.data(), bin.data(), beg.data(), end.data())) return rc;
+  if (int rc = sbam_get_index_refs(c, nullptr, ioff.data(), ob.data(), oe.data(), nm.data(), nu.data())) return rc;
+  const int rc = sbam_bai_assemble(t.n_ref, t.n_runs, ref.data(), bin.data(), beg.data(), end.data(),
+                                   c->idx_intv.data(), ioff.data(), ob.data(), oe.data(), nm.data(), nu.data(),
+                                   t.n_no_coor, out, cap, n_bytes);
+  if (rc) return set_err(c, rc, "sbam_write_bai: %lld bytes needed, capacity %lld", (long long)*n_bytes, (long long)cap);
   return SBAM_OK;
 }
 

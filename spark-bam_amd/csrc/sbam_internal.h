@@ -200,5 +200,39 @@ hipError_t launch_field_sizes(const FieldSizesArgs &a, int64_t *bsum, FieldOffse
                               int64_t *totals, hipStream_t s);
 // field: 0 name, 1 cigar, 2 seq (ASCII bases), 3 qual, 4 aux
 hipError_t launch_field_gather(int field, const FieldGatherArgs &a, hipStream_t s);
+// BAI index from the record columns (sbam_index.hip).  Records in file order; the block table as for
+// launch_record_columns (+ csize: the address behind the last block is where the last record ends).
+struct IndexArgs {
+  const uint8_t *u;
+  int64_t L;
+  const int64_t *roff, *block_pos;
+  const int32_t *block_off, *block_size, *ref_id, *pos;
+  const uint32_t *bin_mq_nl, *flag_nc;
+  int64_t n;
+  int32_t nref;
+  const int64_t *bstart, *buoff;
+  const int32_t *bcsize, *busize;
+  int64_t nblocks, file_base;
+  int32_t *end_out;   // scratch columns, n each: the exclusive reference end and reg2bin(beg, end)
+  uint32_t *bin_out;
+};
+struct IndexStats {  // device words, preset by the host
+  unsigned long long *w;  // [0] first offending stream offset (~0), [1] n_no_coor, [2] n_unsorted, [3] n_runs
+  unsigned long long *n_mapped, *n_unmapped, *off_beg /* ~0 */, *off_end, *n_intv;  // nref each
+};
+struct IndexRuns {  // n entries each
+  int32_t *ref;
+  uint32_t *bin;
+  unsigned long long *beg, *end;
+  int64_t n;
+};
+int64_t index_blocks(int64_t n);  // entries of the passes' heads scratch
+int index_long_cigar_ops();       // a record with more CIGAR ops than this is summed by a whole wave
+// spans, counters, and heads[] = exclusive sums of the run heads per workgroup (st.w[3] = n_runs)
+hipError_t launch_index_pass1(const IndexArgs &a, IndexStats st, int64_t *heads, hipStream_t s);
+// run scatter, linear index into ioffset (preset ~0; reference r's windows at [intv_off[r], intv_off[r + 1])) and
+// its backward fill
+hipError_t launch_index_pass2(const IndexArgs &a, const int64_t *heads, IndexRuns r, const int64_t *intv_off,
+                              unsigned long long *ioffset, hipStream_t s);
 
 }  // namespace sbam

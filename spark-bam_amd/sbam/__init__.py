@@ -136,6 +136,11 @@ class _RecordFieldTotals(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int64) for n in ("name_bytes", "cigar_ops", "seq_bases", "aux_bytes")]
 
 
+class _IndexTotals(ctypes.Structure):
+    _fields_ = [("n_ref", ctypes.c_int32), ("reserved", ctypes.c_int32)] + \
+        [(n, ctypes.c_int64) for n in ("n_runs", "n_intv_total", "n_no_coor", "n_unsorted", "n_records")]
+
+
 # sbam_load_record_fields' mask bits, the data column's dtype, its offsets column and its total
 FIELD_BITS = {"name": 1, "cigar": 2, "seq": 4, "qual": 8, "aux": 16}
 _FIELD_LAYOUT = {"name": (np.uint8, "name_off", "name_bytes"), "cigar": (np.uint32, "cigar_off", "cigar_ops"),
@@ -196,6 +201,13 @@ _SIGNATURES = {  # (restype, argtypes) of every symbol include/sbam.h declares
     "sbam_load_record_fields": (ctypes.c_int, [_vp, _i64, _i64, ctypes.c_uint32, _P(_RecordFieldTotals)]),
     "sbam_get_record_fields": (ctypes.c_int, [_vp, _P(_RecordFields)]),
     "sbam_record_fields_device": (ctypes.c_int, [_vp, _P(_RecordFields), _P(_i64), _P(_i64)]),
+    "sbam_build_index": (ctypes.c_int, [_vp, _P(_IndexTotals)]),
+    "sbam_get_index_runs": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "sbam_get_index_refs": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sbam_bai_assemble": (ctypes.c_int, [_i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
+                                         _P(_i64)]),
+    "sbam_write_bai": (ctypes.c_int, [_vp, _vp, _i64, _P(_i64)]),
+    "sbam_index_long_cigar_ops": (ctypes.c_int, []),
     "sbam_last_kernel_ms": (ctypes.c_double, [_vp, ctypes.c_char_p]),
 }
 EXPORTS = list(_SIGNATURES)
@@ -268,6 +280,41 @@ class Split:
 
     def __str__(self):
         return f"{self.start}-{self.end}"
+
+
+@dataclass
+class IndexRefs:
+    """Linear index and per-reference metadata of a built index (sbam_get_index_refs): reference r's 16 kb windows
+    are ioffset[intv_off[r]:intv_off[r + 1]]; the totals are sbam_build_index's."""
+    intv_off: np.ndarray
+    ioffset: np.ndarray
+    off_beg: np.ndarray
+    off_end: np.ndarray
+    n_mapped: np.ndarray
+    n_unmapped: np.ndarray
+    n_no_coor: int
+    n_unsorted: int
+    n_records: int
+
+
+def bai_assemble(n_ref: int, runs, intv_off, ioffset, off_beg, off_end, n_mapped, n_unmapped, n_no_coor: int) -> bytes:
+    """sbam_bai_assemble (host only, no GPU): runs = (ref int32, bin uint32, beg uint64, end uint64) in file order,
+    the linear index (UINT64_MAX = untouched window) and the per-reference metadata -> .bai bytes."""
+    L = load_library()
+    ref, bn, beg, end = (np.ascontiguousarray(a, t) for a, t in zip(runs, (np.int32, np.uint32, np.uint64, np.uint64)))
+    io, ob, oe = (np.ascontiguousarray(a, np.uint64) for a in (ioffset, off_beg, off_end))
+    iv, nm, nu = (np.ascontiguousarray(a, np.int64) for a in (intv_off, n_mapped, n_unmapped))
+    args = (int(n_ref), ref.size, _ptr(ref), _ptr(bn), _ptr(beg), _ptr(end), _ptr(iv), _ptr(io), _ptr(ob), _ptr(oe),
+            _ptr(nm), _ptr(nu), int(n_no_coor))
+    n = ctypes.c_int64(-1)
+    rc = L.sbam_bai_assemble(*args, None, 0, ctypes.byref(n))
+    if n.value < 0:
+        raise SbamError(f"sbam_bai_assemble: invalid arguments ({rc})")
+    out = np.zeros(n.value, np.uint8)
+    rc = L.sbam_bai_assemble(*args, _ptr(out), out.size, ctypes.byref(n))
+    if rc != SBAM_OK:
+        raise SbamError(f"sbam_bai_assemble: {rc}")
+    return out.tobytes()
 
 
 def _pos(p: _Pos) -> Pos:
@@ -358,6 +405,7 @@ class BamFile:
         self.contig_lengths = None
         self.header_end = None
         self.n_loaded = 0  # records of the last load_records still on the device
+        self._index = None  # totals of the last build_index
         if inflate:
             self.inflate()
             if contig_lengths is not None:
@@ -686,6 +734,56 @@ class BamFile:
         self._check(self.L.sbam_get_record_fields(self.ctx, ctypes.byref(rf)))
         return out
 
+    # ---- BAI writer
+    def build_index(self, split_size: int = LOCAL_FS_BLOCK_SIZE, use_success_bitmap: bool = False) -> dict:
+        """sbam_build_index over the whole file's records; they are loaded first (load_records over every split of
+        `split_size`) when the context does not hold them.  Returns the totals."""
+        t = _IndexTotals()
+        rc = self.L.sbam_build_index(self.ctx, ctypes.byref(t))
+        if rc == ERR_STATE and self.base_offset == 0 and self.file_size == self._buf.size \
+                and self.uncompressed_size is not None:
+            self.load_records(split_size, use_success_bitmap=use_success_bitmap, columns=None)
+            rc = self.L.sbam_build_index(self.ctx, ctypes.byref(t))
+        self._check(rc)
+        self._index = {k: int(getattr(t, k)) for k, _ in _IndexTotals._fields_ if k != "reserved"}
+        return self._index
+
+    def index_runs(self):
+        """The raw runs of the last build_index / build_bai in file order: (ref int32, bin uint32, beg uint64,
+        end uint64), one entry per maximal stretch of records with the same (ref_id, bin)."""
+        if self._index is None:
+            raise SbamError("build_index has not run")
+        n = self._index["n_runs"]
+        ref, bn, beg, end = np.zeros(n, np.int32), np.zeros(n, np.uint32), np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        self._check(self.L.sbam_get_index_runs(self.ctx, _ptr(ref), _ptr(bn), _ptr(beg), _ptr(end)))
+        return ref, bn, beg, end
+
+    def index_refs(self) -> IndexRefs:
+        """The linear index (after the fill) and the per-reference metadata of the last build_index / build_bai."""
+        if self._index is None:
+            raise SbamError("build_index has not run")
+        t = self._index
+        nr = t["n_ref"]
+        iv, io = np.zeros(nr + 1, np.int64), np.zeros(t["n_intv_total"], np.uint64)
+        ob, oe, nm, nu = np.zeros(nr, np.uint64), np.zeros(nr, np.uint64), np.zeros(nr, np.int64), np.zeros(nr, np.int64)
+        self._check(self.L.sbam_get_index_refs(self.ctx, _ptr(iv), _ptr(io), _ptr(ob), _ptr(oe), _ptr(nm), _ptr(nu)))
+        return IndexRefs(iv, io, ob, oe, nm, nu, t["n_no_coor"], t["n_unsorted"], t["n_records"])
+
+    def build_bai(self, split_size: int = LOCAL_FS_BLOCK_SIZE, require_sorted: bool = True,
+                  use_success_bitmap: bool = False) -> bytes:
+        """The file's .bai bytes (SAM spec §5.2), built on the GPU from the decoded record columns (sbam_build_index,
+        sbam_write_bai).  A file whose records are not in coordinate order raises SbamError("unsorted positions")
+        unless require_sorted is False (the index is defined for any order; readers assume a sorted file)."""
+        t = self.build_index(split_size, use_success_bitmap)
+        if require_sorted and t["n_unsorted"] > 0:
+            raise SbamError("unsorted positions")
+        n = ctypes.c_int64(0)
+        if self.L.sbam_write_bai(self.ctx, None, 0, ctypes.byref(n)) == ERR_STATE:
+            self._check(ERR_STATE)
+        out = np.zeros(n.value, np.uint8)
+        self._check(self.L.sbam_write_bai(self.ctx, _ptr(out), out.size, ctypes.byref(n)))
+        return out.tobytes()
+
     def record_spans(self, offsets: np.ndarray):
         """(ref_id, start, end) of the records at `offsets`: [getStart - 1, getEnd) as CanLoadBam.region uses it
         (unmapped: end 0)."""
@@ -707,15 +805,18 @@ class BamFile:
             return self.uncompressed_size
         raise SbamError(f"no BGZF block at {b}")
 
-    def load_bam_intervals(self, bai: bytes, loci: str, split_size: int = 32 << 20, ratio: float = 3.0):
+    def load_bam_intervals(self, bai: Optional[bytes] = None, loci: str = "", split_size: int = 32 << 20, ratio: float = 3.0):
         """sc.loadBamIntervals (CanLoadBam.scala:59-138): the BAI chunks overlapping `loci` (htsjdk getFileSpan,
         sbam.bai), grouped into partitions by estimated size (cappedCostGroups), and per chunk the records from
         chunk.start while Pos < chunk.end whose [getStart - 1, getEnd) intersects the loci.  Record chains and
         reference spans run on the GPU (sbam_record_offsets, sbam_record_spans).  Returns (chunks, partitions):
         partitions = per partition, the record stream offsets kept, in file order.  (The MaxSplitSize default of
-        32 MiB is hammerlab's, outside the reference tree: parity unpinned.)"""
+        32 MiB is hammerlab's, outside the reference tree: parity unpinned.)  `bai=None`: the index is built here
+        (build_bai), so a file without a sidecar index works."""
         from sbam import bai as B
         from sbam.cli import header_names
+        if bai is None:
+            bai = self.build_bai()
         refs = B.parse_bai(bai)
         names = header_names(self)
         q = []

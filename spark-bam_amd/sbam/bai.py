@@ -93,6 +93,22 @@ def parse_bai(data: bytes) -> List[Reference]:
     return refs
 
 
+def parse_n_no_coor(data: bytes) -> Optional[int]:
+    """The optional trailing n_no_coor (SAM spec §5.2: the records without coordinates) of .bai bytes, None when the
+    file ends behind its last reference."""
+    (n_ref,) = struct.unpack_from("<i", data, 4)
+    p = 8
+    for _ in range(n_ref):
+        (n_bin,) = struct.unpack_from("<i", data, p)
+        p += 4
+        for _ in range(n_bin):
+            (n_chunk,) = struct.unpack_from("<i", data, p + 4)
+            p += 8 + 16 * n_chunk
+        (n_intv,) = struct.unpack_from("<i", data, p)
+        p += 4 + 8 * n_intv
+    return struct.unpack_from("<Q", data, p)[0] if len(data) >= p + 8 else None
+
+
 def region_to_bins(start: int, end: int) -> Optional[List[int]]:
     """GenomicIndexUtil.regionToBins: 1-based closed [start, end]."""
     mx = 0x1FFFFFFF

@@ -1,5 +1,5 @@
 """spark-bam CLI drop-ins over the GPU path: `full-check`, `check-bam -s`, `check-blocks -s`, `compute-splits -s`,
-`count-reads`, `index-blocks`, `index-records`.
+`count-reads`, `index-blocks`, `index-records`, `index-bam`.
 
     python -m sbam.cli full-check [-l LIMIT] [-m SPLIT] [-i RANGES] [-r READS] [--gpus N | --windows W] BAM [OUT]
     python -m sbam.cli check-bam -s [-l LIMIT] [-m SPLIT] [-i RANGES] BAM [OUT]
@@ -9,6 +9,7 @@
     python -m sbam.cli compute-splits [-s] [-l LIMIT] [-m SPLIT] BAM [OUT]
     python -m sbam.cli count-reads [-m SPLIT] BAM [OUT]
     python -m sbam.cli view [-h] [-m SPLIT] BAM [OUT]
+    python -m sbam.cli index-bam [-o OUT] [--allow-unsorted] [-m SPLIT] BAM
 
 Report text follows the reference apps line for line, so the goldens of cli/src/test/resources/output/ diff
 verbatim (tests/test_cli.py):
@@ -23,6 +24,8 @@ verbatim (tests/test_cli.py):
   * count-reads: compare/CountReads.scala:80-100, spark-bam side only;
   * view: the records of loadReads (CanLoadBam.scala:348-352) as SAM text (sbam.sam; pinned by the reference's 2.sam
     and 5k.sam), decoded on the GPU by sbam_load_record_fields.
+  * index-bam: the `.bai` sidecar (SAM spec §5.2; what `samtools index` writes and the reference's
+    check/.../bam/index/Index.scala:53-90 reads), built on the GPU by sbam_build_index.
 Counting, checking and splitting all run through libsbam.so (sbam.BamFile); this module only formats."""
 from __future__ import annotations
 
@@ -677,6 +680,23 @@ def view_main(a) -> int:
     return 0
 
 
+def index_bam_main(a) -> int:
+    """BAM.bai (or -o OUT) from BamFile.build_bai.  A file whose records are out of coordinate order is refused, as
+    samtools refuses it, unless --allow-unsorted: exit status 1, `unsorted positions` on stderr, nothing written."""
+    data = open(a.bam, "rb").read()
+    with sbam.BamFile(data, path=a.bam) as f:
+        try:
+            bai = f.build_bai(sbam.effective_split_size(a.max_split_size), require_sorted=not a.allow_unsorted)
+        except sbam.SbamError as e:
+            if str(e) != "unsorted positions":
+                raise
+            sys.stderr.write(f"{a.bam}: unsorted positions\n")
+            return 1
+    with open(a.out or a.bam + ".bai", "wb") as fh:
+        fh.write(bai)
+    return 0
+
+
 def write_report(lines: Sequence[str], out: Optional[str]):
     """The report text to the file `out`, or to stdout."""
     text = "\n".join(lines) + "\n"
@@ -695,6 +715,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     p.add_argument("-m", "--max-split-size", type=parse_bytes, default=None)
     p.add_argument("bam")
     p.add_argument("out", nargs="?")
+    p = sub.add_parser("index-bam")
+    p.add_argument("-o", "--out", default=None, help="default: BAM.bai")
+    p.add_argument("--allow-unsorted", action="store_true")
+    p.add_argument("-m", "--max-split-size", type=parse_bytes, default=None)
+    p.add_argument("bam")
     for name in ("full-check", "check-bam", "check-blocks", "compute-splits", "count-reads", "index-blocks",
                  "index-records"):
         p = sub.add_parser(name)
@@ -720,6 +745,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     a = ap.parse_args(argv)
     if a.cmd == "view":
         return view_main(a)
+    if a.cmd == "index-bam":
+        return index_bam_main(a)
     if getattr(a, "gpus", 1) > 1:
         if "WORLD_SIZE" not in os.environ:
             return spawn_ranks(a.gpus, sys.argv[1:] if argv is None else argv)
