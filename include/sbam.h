@@ -35,6 +35,8 @@ extern "C" {
 #define SBAM_ERR_HALO 9           /* a check needed bytes past a shard's loaded range (grow the halo)       */
 #define SBAM_ERR_RECORD 10        /* variable-length fields overrun block_size, or (sbam_build_index) a record no
                                      BAI can index; error.position = record offset                          */
+#define SBAM_ERR_CRC 11           /* a block's inflated bytes do not have the CRC32 its footer stores; error.position =
+                                     the block's file offset, error.expected = stored, error.actual = computed */
 
 typedef struct sbam_ctx sbam_ctx;
 
@@ -141,6 +143,37 @@ int sbam_inflate(sbam_ctx *ctx, int64_t *uncompressed_size);
 /* Blocks the last sbam_inflate handed from the wave-parallel decoder to the exact per-lane one (stored or
  * invalid blocks, incomplete codes, streams that end before ISIZE or run past it); for parity tests and profiles. */
 int sbam_inflate_fallbacks(sbam_ctx *ctx, int64_t *n);
+
+/* ---- BGZF block CRC32 check -------------------------------------------------------------------------- */
+
+typedef struct {
+  int64_t n_blocks;  /* blocks checked */
+  int64_t n_bad;     /* blocks whose computed CRC32 differs from the footer's */
+  int64_t first_bad; /* table index of the first of them, -1: none */
+  int64_t bytes;     /* uncompressed bytes of the checked blocks */
+} sbam_crc_totals;
+
+/* CRC32 (IEEE, as zlib's crc32) of the inflated bytes of blocks [b0, b1) of the table, computed on the GPU from the
+ * resident stream and compared with the value each block's footer stores; b1 < 0: through the last block.  The
+ * reference has no counterpart: Stream.scala:49-54 enforces ISIZE and never reads the CRC.  The behaviour mirrored is
+ * htslib's bgzf reader, which checks every block it inflates (`bgzip -t`), and htsjdk's setCheckCrcs.  A checker:
+ * SBAM_OK when it ran, whether or not blocks mismatch (*totals says).  SBAM_ERR_STATE before a successful
+ * sbam_inflate and after sbam_reset, sbam_load or a sbam_reserve that dropped the stages (the results belong to the
+ * stream stage and go with it; sbam_reserve does not size their buffers); SBAM_ERR_ARG for a range outside the table;
+ * b0 == b1 is valid and gives zero totals. */
+int sbam_check_crc(sbam_ctx *ctx, int64_t b0, int64_t b1, sbam_crc_totals *totals);
+
+/* Copy the computed and stored CRC32s of blocks [b0, b0 + n) from the last sbam_check_crc (either pointer may be
+ * NULL).  Blocks outside the range it checked, or no check since the stream was made: SBAM_ERR_STATE.  (No reference
+ * counterpart, as above: Stream.scala:49-54; htslib's bgzf check compares the same two values per block.) */
+int sbam_get_block_crcs(sbam_ctx *ctx, int64_t b0, int64_t n, uint32_t *computed, uint32_t *stored);
+
+/* on != 0: every later sbam_inflate checks the whole table after a successful inflate and fails with SBAM_ERR_CRC
+ * ("CRC32 mismatch in block at <file offset>: footer <%08x>, computed <%08x>") on the first block that mismatches,
+ * leaving the stream stage unset as after SBAM_ERR_INFLATE.  Sticky across sbam_reset and sbam_load; default off.
+ * (No reference counterpart: Stream.scala:49-54 never reads the CRC; this is htslib's bgzf check, htsjdk's
+ * setCheckCrcs(true).) */
+int sbam_set_verify_crc(sbam_ctx *ctx, int32_t on);
 
 /* Copy uncompressed bytes [off, off+len) of the stream to the host. */
 int sbam_read_uncompressed(sbam_ctx *ctx, int64_t off, int64_t len, uint8_t *out);
@@ -370,7 +403,7 @@ int sbam_index_long_cigar_ops(void);
 /* Device time (ms, HIP events on the library's stream) of the most recent launch of a named kernel
  * family: "scan", "inflate", "check_full", "check_eager", "records", "load_records", "record_fields" (the gather of
  * sbam_load_record_fields; "record_field_sizes": its sizes and scan), "index" (sbam_build_index, from its first pass
- * through the linear index's fill). Returns -1 if none. */
+ * through the linear index's fill), "crc" (the block CRC32 check). Returns -1 if none. */
 double sbam_last_kernel_ms(sbam_ctx *ctx, const char *kernel);
 
 #ifdef __cplusplus

@@ -213,6 +213,11 @@ struct sbam_ctx {
   DevBuf<int32_t> d_slow;        // blocks the wave decoder hands to the exact per-lane decoder
   DevBuf<unsigned int> d_icnt;   // slow-path blocks, slow-path work, resolve work, stored-only blocks
   int64_t inflate_slow = -1;     // blocks the last sbam_inflate decoded on the exact per-lane path
+  // CRC32 check of the stream's blocks (sbam_check_crc): computed and stored values by table index, and the range
+  // [crc_b0, crc_b1) the last check filled (-1: none); they belong to the stream stage and go with it
+  DevBuf<uint32_t> d_crc, d_crcst;
+  int64_t crc_b0 = -1, crc_b1 = -1;
+  bool verify_crc = false;  // sbam_set_verify_crc: sticky across reset and load
   // contig lengths
   int32_t nref = -1;
   DevBuf<int64_t> d_lens;
@@ -326,6 +331,7 @@ hipError_t drop_stages(sbam_ctx *c) {
   const hipError_t e = c->blk.invalidate();
   c->L = -1;
   c->inflate_slow = -1;
+  c->crc_b0 = c->crc_b1 = -1;
   drop_bitmap(c);
   c->n_loaded = -1;
   c->f_n = -1;
@@ -360,6 +366,11 @@ hipError_t ensure_inflate(sbam_ctx *c, int64_t L, int64_t nb, bool *grew = nullp
   HIPTRY(c->d_tokbase.ensure(nb, grew));
   HIPTRY(c->d_slow.ensure(2 * nb, grew));  // (the exact decoder's list, then the stored-only list)
   return c->d_icnt.ensure(4);
+}
+// the CRC check's computed and stored values, one per block of the table
+hipError_t ensure_crc(sbam_ctx *c, int64_t nb, bool *grew = nullptr) {
+  HIPTRY(c->d_crc.ensure((size_t)nb, grew));
+  return c->d_crcst.ensure((size_t)nb, grew);
 }
 // bitmap words covering [x0 & ~63, x1)
 hipError_t ensure_bitmap(sbam_ctx *c, int64_t x0, int64_t x1, bool *grew = nullptr) {
@@ -743,6 +754,8 @@ int sbam_get_blocks(sbam_ctx *c, int64_t *start, int32_t *csize, int32_t *usize,
   return SBAM_OK;
 }
 
+static int run_crc(sbam_ctx *c, int64_t L, int64_t b0, int64_t b1, unsigned long long bad[2]);
+
 int sbam_inflate(sbam_ctx *c, int64_t *usz) {
   if (!c) return SBAM_ERR_ARG;
   if (c->blk.n < 0) return set_err(c, SBAM_ERR_STATE, "sbam_scan_blocks has not run");
@@ -750,6 +763,7 @@ int sbam_inflate(sbam_ctx *c, int64_t *usz) {
   int64_t L = 0;
   HIPCHK(c, c->blk.total(&L));  // (the table's host copy is picked up below, while the decoder runs)
   const int64_t nb = c->blk.n;
+  c->crc_b0 = c->crc_b1 = -1;  // (a check's results describe the stream this call replaces)
   HIPCHK(c, ensure_inflate(c, L, nb));
   HIPCHK(c, hipMemsetAsync(c->d_u + L, 0, kStreamPad, c->stream));
   int32_t *d_status = c->d_status, *d_found = c->d_found;
@@ -807,9 +821,92 @@ int sbam_inflate(sbam_ctx *c, int64_t *usz) {
     c->err.actual = found;
     return set_err(c, SBAM_ERR_INFLATE, "Expected %d decompressed bytes, found %d", c->blk.usize[ferr], found);
   }
+  if (c->verify_crc) {  // htslib's bgzf check: every block's inflated bytes against its footer, before the stream is set
+    unsigned long long bad[2];
+    const int rc = run_crc(c, L, 0, nb, bad);
+    if (rc) return rc;
+    if (bad[0]) {
+      const int64_t b = (int64_t)bad[1];
+      uint32_t got = 0, want = 0;
+      HIPCHK(c, hipMemcpy(&got, c->d_crc + b, 4, hipMemcpyDeviceToHost));
+      HIPCHK(c, hipMemcpy(&want, c->d_crcst + b, 4, hipMemcpyDeviceToHost));
+      c->err.position = c->base + c->blk.start[b];
+      c->err.expected = want;
+      c->err.actual = got;
+      c->L = -1;
+      return set_err(c, SBAM_ERR_CRC, "CRC32 mismatch in block at %lld: footer %08x, computed %08x",
+                     (long long)c->err.position, want, got);
+    }
+    c->crc_b0 = 0;
+    c->crc_b1 = nb;
+  }
   c->L = L;
   drop_bitmap(c);
   if (usz) *usz = L;
+  return SBAM_OK;
+}
+
+// ---- CRC32 check ------------------------------------------------------------------------------------
+// blocks [b0, b1) of the table against their footers, over the stream of L bytes in d_u; bad[0] = mismatches,
+// bad[1] = the first one's table index (~0: none)
+static int run_crc(sbam_ctx *c, int64_t L, int64_t b0, int64_t b1, unsigned long long bad[2]) {
+  const int64_t nb = c->blk.n;
+  HIPCHK(c, ensure_crc(c, nb));
+  unsigned long long *d_bad = reinterpret_cast<unsigned long long *>(c->d_small + 24);
+  bad[0] = 0;
+  bad[1] = ~0ull;
+  HIPCHK(c, hipMemcpyAsync(d_bad, bad, 16, hipMemcpyHostToDevice, c->stream));
+  {
+    Timer t(c, "crc");
+    const BlockTable bt{c->d_bstart, c->d_bh, c->d_bc, c->d_bu, c->d_buoff, nb};
+    HIPCHK(c, launch_block_crc(c->d_comp, c->D, c->d_u, L, bt, b0, b1, c->d_crc, c->d_crcst, d_bad, d_bad + 1,
+                               c->stream));
+  }
+  HIPCHK(c, hipMemcpyAsync(bad, d_bad, 16, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SBAM_OK;
+}
+
+int sbam_set_verify_crc(sbam_ctx *c, int32_t on) {
+  if (!c) return SBAM_ERR_ARG;
+  c->verify_crc = on != 0;
+  return SBAM_OK;
+}
+
+int sbam_check_crc(sbam_ctx *c, int64_t b0, int64_t b1, sbam_crc_totals *totals) {
+  if (!c) return SBAM_ERR_ARG;
+  if (c->L < 0) return set_err(c, SBAM_ERR_STATE, "sbam_inflate has not run");
+  int rc = ensure_blocks(c);
+  if (rc) return rc;
+  const int64_t nb = c->blk.n;
+  if (b1 < 0) b1 = nb;
+  if (b0 < 0 || b0 > b1 || b1 > nb)
+    return set_err(c, SBAM_ERR_ARG, "blocks [%lld, %lld) outside the table of %lld", (long long)b0, (long long)b1,
+                   (long long)nb);
+  HIPCHK(c, hipSetDevice(c->device));
+  unsigned long long bad[2];
+  rc = run_crc(c, c->L, b0, b1, bad);
+  if (rc) return rc;
+  c->crc_b0 = b0;
+  c->crc_b1 = b1;
+  if (totals) {
+    totals->n_blocks = b1 - b0;
+    totals->n_bad = (int64_t)bad[0];
+    totals->first_bad = bad[1] == ~0ull ? -1 : (int64_t)bad[1];
+    totals->bytes = c->blk.uoff[b1] - c->blk.uoff[b0];
+  }
+  return SBAM_OK;
+}
+
+int sbam_get_block_crcs(sbam_ctx *c, int64_t b0, int64_t n, uint32_t *computed, uint32_t *stored) {
+  if (!c || b0 < 0 || n < 0) return SBAM_ERR_ARG;
+  if (c->L < 0 || c->crc_b0 < 0) return set_err(c, SBAM_ERR_STATE, "sbam_check_crc has not run");
+  if (b0 < c->crc_b0 || b0 + n > c->crc_b1)
+    return set_err(c, SBAM_ERR_STATE, "blocks [%lld, %lld) outside the checked range [%lld, %lld)", (long long)b0,
+                   (long long)(b0 + n), (long long)c->crc_b0, (long long)c->crc_b1);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (n && computed) HIPCHK(c, hipMemcpy(computed, c->d_crc + b0, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (n && stored) HIPCHK(c, hipMemcpy(stored, c->d_crcst + b0, (size_t)n * 4, hipMemcpyDeviceToHost));
   return SBAM_OK;
 }
 

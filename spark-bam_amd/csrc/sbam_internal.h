@@ -118,6 +118,12 @@ hipError_t launch_inflate_redo(const uint8_t *d, int64_t D, BlockTable bt, TokPo
 // first_err = min block index with status != 0 (caller presets ~0)
 hipError_t launch_first_error(const int32_t *status, int64_t n, unsigned long long *first_err, hipStream_t s);
 hipError_t launch_lower_bound(const Candidate *c, int64_t n, int64_t q, int64_t *out, hipStream_t s);
+// CRC32 of the inflated bytes of blocks [b0, b1) against the footers' (sbam_crc.hip): crc[b] computed, stored[b] the
+// little-endian u32 at comp[start[b] + csize[b] - 8]; *n_bad += mismatches, *first_bad = min(*first_bad, their
+// indices) (the caller presets 0 and ~0).  u: the stream of L bytes with its kStreamPad behind it.
+hipError_t launch_block_crc(const uint8_t *comp, int64_t D, const uint8_t *u, int64_t L, BlockTable bt, int64_t b0,
+                            int64_t b1, uint32_t *crc, uint32_t *stored, unsigned long long *n_bad,
+                            unsigned long long *first_bad, hipStream_t s);
 // Bitmaps cover [x0 & ~63, x1): bit (x - (x0 & ~63)) = call at x (0 for x < x0).
 // *tiles_counted: whether cd.tile_pass0 now holds every tile's PASS0 count (the bit-sliced pass ran)
 hipError_t launch_check_full_counts(StreamView sv, int64_t x0, int64_t x1, int32_t R, int32_t by_key, CountsDev cd,

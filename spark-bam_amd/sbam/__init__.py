@@ -29,6 +29,7 @@ SBAM_OK = 0
 ERR_HEADER_PARSE, ERR_HEADER_SEARCH, ERR_INFLATE, ERR_NO_READ_FOUND, ERR_NOT_BAM, ERR_ARG, ERR_HIP, ERR_STATE, \
     ERR_HALO = range(1, 10)
 ERR_RECORD = 10
+ERR_CRC = 11
 
 FLAG_NAMES = [  # check/src/main/scala/org/hammerlab/bam/check/full/error/Flags.scala:201-223
     "tooFewFixedBlockBytes", "negativeReadIdx", "tooLargeReadIdx", "negativeReadPos", "tooLargeReadPos",
@@ -87,8 +88,15 @@ class RecordFieldsException(SbamError):
     code = ERR_RECORD
 
 
+class CrcException(IOError, SbamError):
+    """A BGZF block whose inflated bytes do not have the CRC32 its footer stores (verify_crc): `position` is the
+    block's file offset, `expected` the stored value, `actual` the computed one."""
+    code = ERR_CRC
+    position = expected = actual = None
+
+
 _EXC = {c.code: c for c in (HeaderParseException, HeaderSearchFailedException, InflateException,
-                            NoReadFoundException, HaloException, RecordFieldsException)}
+                            NoReadFoundException, HaloException, RecordFieldsException, CrcException)}
 
 
 class _Pos(ctypes.Structure):
@@ -141,6 +149,10 @@ class _IndexTotals(ctypes.Structure):
         [(n, ctypes.c_int64) for n in ("n_runs", "n_intv_total", "n_no_coor", "n_unsorted", "n_records")]
 
 
+class _CrcTotals(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ("n_blocks", "n_bad", "first_bad", "bytes")]
+
+
 # sbam_load_record_fields' mask bits, the data column's dtype, its offsets column and its total
 FIELD_BITS = {"name": 1, "cigar": 2, "seq": 4, "qual": 8, "aux": 16}
 _FIELD_LAYOUT = {"name": (np.uint8, "name_off", "name_bytes"), "cigar": (np.uint32, "cigar_off", "cigar_ops"),
@@ -179,6 +191,9 @@ _SIGNATURES = {  # (restype, argtypes) of every symbol include/sbam.h declares
     "sbam_get_blocks": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64]),
     "sbam_inflate": (ctypes.c_int, [_vp, _P(_i64)]),
     "sbam_inflate_fallbacks": (ctypes.c_int, [_vp, _P(_i64)]),
+    "sbam_check_crc": (ctypes.c_int, [_vp, _i64, _i64, _P(_CrcTotals)]),
+    "sbam_get_block_crcs": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp]),
+    "sbam_set_verify_crc": (ctypes.c_int, [_vp, _i32]),
     "sbam_read_uncompressed": (ctypes.c_int, [_vp, _i64, _i64, _vp]),
     "sbam_pos_to_offset": (ctypes.c_int, [_vp, _Pos, _P(_i64)]),
     "sbam_offset_to_pos": (ctypes.c_int, [_vp, _i64, _P(_Pos)]),
@@ -387,7 +402,8 @@ class BamFile:
     (load/.../spark/load/Channels.scala:15-26) with the hot path behind it."""
 
     def __init__(self, data, device: int = 0, base_offset: int = 0, file_size: Optional[int] = None,
-                 path: str = "<bytes>", inflate: bool = True, contig_lengths: Optional[Sequence[int]] = None):
+                 path: str = "<bytes>", inflate: bool = True, contig_lengths: Optional[Sequence[int]] = None,
+                 verify_crc: bool = False):
         self.L = load_library()
         buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
         self._buf = np.ascontiguousarray(buf)
@@ -399,6 +415,10 @@ class BamFile:
                               ctypes.byref(self.ctx))
         self._check(rc)
         self._check(self.L.sbam_set_path(self.ctx, str(path).encode()))
+        self._crc = None  # (b0, b1) of the last check_crc
+        self.verify_crc = False
+        if verify_crc:
+            self.set_verify_crc(True)
         self.n_blocks = self._scan()
         self.uncompressed_size = None
         self.n_ref = None
@@ -419,7 +439,10 @@ class BamFile:
             return
         e = self.L.sbam_last_error(self.ctx).contents if self.ctx else None
         msg = e.message.decode() if e else f"sbam error {rc}"
-        raise _EXC.get(rc, SbamError)(msg)
+        exc = _EXC.get(rc, SbamError)(msg)
+        if rc == ERR_CRC and e:
+            exc.position, exc.expected, exc.actual = int(e.position), int(e.expected), int(e.actual)
+        raise exc
 
     def close(self):
         if self.ctx:
@@ -454,6 +477,7 @@ class BamFile:
         self.n_blocks = None
         self.uncompressed_size = None
         self.n_loaded = 0
+        self._crc = None
 
     def reserve(self, comp_bytes: int, n_blocks: int, ubytes: int, n_records: int = 0):
         """sbam_reserve: size the device buffers for windows up to these sizes, so no later load reallocates.  A
@@ -480,6 +504,7 @@ class BamFile:
         self.n_blocks = None
         self.uncompressed_size = None
         self.n_loaded = 0
+        self._crc = None
 
     def run(self, contig_lengths: Optional[Sequence[int]] = None):
         """Scan → inflate → header/contig lengths from the resident compressed bytes."""
@@ -518,7 +543,10 @@ class BamFile:
 
     def inflate(self) -> int:
         n = ctypes.c_int64(0)
+        self._crc = None
         self._check(self.L.sbam_inflate(self.ctx, ctypes.byref(n)))
+        if self.verify_crc and self.n_blocks is not None:  # (the context checked the whole table)
+            self._crc = (0, int(self.n_blocks))
         self.uncompressed_size = n.value
         return n.value
 
@@ -527,6 +555,43 @@ class BamFile:
         n = ctypes.c_int64(0)
         self._check(self.L.sbam_inflate_fallbacks(self.ctx, ctypes.byref(n)))
         return n.value
+
+    # ---- block CRC32 check
+    def set_verify_crc(self, on: bool = True):
+        """sbam_set_verify_crc: every later inflate checks each block's CRC32 against its footer and raises
+        CrcException on the first mismatch (htslib's bgzf check; htsjdk's setCheckCrcs).  Sticky across reset and
+        load; off by default."""
+        self._check(self.L.sbam_set_verify_crc(self.ctx, 1 if on else 0))
+        self.verify_crc = bool(on)
+
+    def check_crc(self, b0: int = 0, b1: Optional[int] = None) -> dict:
+        """sbam_check_crc over blocks [b0, b1) of the table (b1=None: through the last): the totals (n_blocks, n_bad,
+        first_bad, bytes) plus `bad`, the mismatching blocks' table indices (int64), and `bad_offsets`, their file
+        offsets."""
+        t = _CrcTotals()
+        self._crc = None
+        self._check(self.L.sbam_check_crc(self.ctx, int(b0), -1 if b1 is None else int(b1), ctypes.byref(t)))
+        out = {k: int(getattr(t, k)) for k, _ in _CrcTotals._fields_}
+        self._crc = (int(b0), int(b0) + out["n_blocks"])
+        if out["n_bad"]:
+            computed, stored = self.block_crcs()
+            bad = int(b0) + np.flatnonzero(computed != stored).astype(np.int64)
+        else:
+            bad = np.zeros(0, np.int64)
+        out["bad"] = bad
+        out["bad_offsets"] = self.blocks()[0][bad] if bad.size else np.zeros(0, np.int64)
+        return out
+
+    def block_crcs(self, b0: Optional[int] = None, n: Optional[int] = None):
+        """(computed, stored) CRC32s as uint32 arrays for blocks [b0, b0 + n) of the last check_crc (default: the
+        range it checked; after an inflate with verify_crc, the whole table).  Blocks it did not check: SbamError."""
+        if b0 is None:
+            b0 = self._crc[0] if self._crc else 0
+        if n is None:
+            n = (self._crc[1] if self._crc else (self.n_blocks or 0)) - b0
+        computed, stored = np.zeros(max(n, 0), np.uint32), np.zeros(max(n, 0), np.uint32)
+        self._check(self.L.sbam_get_block_crcs(self.ctx, int(b0), int(n), _ptr(computed), _ptr(stored)))
+        return computed, stored
 
     def read_uncompressed(self, off: int, length: int) -> bytes:
         out = np.zeros(length, np.uint8)

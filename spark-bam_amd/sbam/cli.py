@@ -8,8 +8,9 @@
     python -m sbam.cli index-records BAM [OUT]
     python -m sbam.cli compute-splits [-s] [-l LIMIT] [-m SPLIT] BAM [OUT]
     python -m sbam.cli count-reads [-m SPLIT] BAM [OUT]
-    python -m sbam.cli view [-h] [-m SPLIT] BAM [OUT]
-    python -m sbam.cli index-bam [-o OUT] [--allow-unsorted] [-m SPLIT] BAM
+    python -m sbam.cli view [-h] [-m SPLIT] [--verify-crc] BAM [OUT]
+    python -m sbam.cli index-bam [-o OUT] [--allow-unsorted] [--verify-crc] [-m SPLIT] BAM
+    python -m sbam.cli check-crc [-l LIMIT] [--windows W] BAM [OUT]
 
 Report text follows the reference apps line for line, so the goldens of cli/src/test/resources/output/ diff
 verbatim (tests/test_cli.py):
@@ -26,6 +27,9 @@ verbatim (tests/test_cli.py):
     and 5k.sam), decoded on the GPU by sbam_load_record_fields.
   * index-bam: the `.bai` sidecar (SAM spec §5.2; what `samtools index` writes and the reference's
     check/.../bam/index/Index.scala:53-90 reads), built on the GPU by sbam_build_index.
+  * check-crc: every BGZF block's CRC32 against its footer (no reference counterpart: Stream.scala:49-54 never reads
+    it; what `bgzip -t` checks), computed on the GPU by sbam_check_crc; --verify-crc makes view and index-bam check it
+    while they load.
 Counting, checking and splitting all run through libsbam.so (sbam.BamFile); this module only formats."""
 from __future__ import annotations
 
@@ -668,12 +672,15 @@ def view_main(a) -> int:
     data = open(a.bam, "rb").read()
     out = open(a.out, "wb") if a.out else sys.stdout.buffer  # bytes as stored (names and tags are not re-encoded)
     try:
-        with sbam.BamFile(data, path=a.bam) as f:
+        with sbam.BamFile(data, path=a.bam, verify_crc=a.verify_crc) as f:
             if a.header:
                 text = header_text(f)
                 out.write((text if not text or text.endswith("\n") else text + "\n").encode("latin-1"))
             for ln in view_lines(f, sbam.effective_split_size(a.max_split_size)):
                 out.write(ln.encode("latin-1") + b"\n")
+    except sbam.CrcException as e:
+        sys.stderr.write(f"{a.bam}: {e}\n")
+        return 1
     finally:
         if a.out:
             out.close()
@@ -684,7 +691,12 @@ def index_bam_main(a) -> int:
     """BAM.bai (or -o OUT) from BamFile.build_bai.  A file whose records are out of coordinate order is refused, as
     samtools refuses it, unless --allow-unsorted: exit status 1, `unsorted positions` on stderr, nothing written."""
     data = open(a.bam, "rb").read()
-    with sbam.BamFile(data, path=a.bam) as f:
+    try:
+        f = sbam.BamFile(data, path=a.bam, verify_crc=a.verify_crc)
+    except sbam.CrcException as e:
+        sys.stderr.write(f"{a.bam}: {e}\n")
+        return 1
+    with f:
         try:
             bai = f.build_bai(sbam.effective_split_size(a.max_split_size), require_sorted=not a.allow_unsorted)
         except sbam.SbamError as e:
@@ -695,6 +707,34 @@ def index_bam_main(a) -> int:
     with open(a.out or a.bam + ".bai", "wb") as fh:
         fh.write(bai)
     return 0
+
+
+# ---- check-crc ---------------------------------------------------------------------------------------------
+def check_crc_lines(n_blocks: int, n_bytes: int, bad: Sequence[Tuple[int, int, int]], limit: int) -> List[str]:
+    """The check-crc report: blocks and uncompressed bytes checked, then `All CRC32s match` or the mismatching blocks
+    as (file offset, stored, computed), at most `limit` of them."""
+    out = [f"{n_blocks} blocks, {n_bytes} uncompressed bytes checked"]
+    if not bad:
+        return out + ["All CRC32s match"]
+    header = f"{len(bad)} of {n_blocks} blocks with a CRC32 mismatch:"
+    print_limited(out, [f"{o}: footer {s:08x}, computed {c:08x}" for o, s, c in bad], None, header,
+                  lambda n: header, limit)
+    return out
+
+
+def check_crc_main(a) -> int:
+    """Every BGZF block's CRC32 checked on the GPU (what `bgzip -t` checks), in --windows byte-range windows (0: as
+    many as the file's size and free HBM need).  Exit status 0 when all match, 1 otherwise."""
+    from sbam import dist as sdist
+    dev = a.device or 0
+    windows = a.windows
+    if windows == 0:
+        src, size = sdist.file_source(a.bam)
+        margin = int(sdist.hbm_bytes_per_compressed_byte(3.3) * (128 << 20))
+        windows = sdist.auto_windows(size, src, max(1, sdist.device_free_bytes(dev) - margin), contexts=1)
+    r = sdist.check_crc_file(a.bam, world=windows, device=dev)
+    write_report(check_crc_lines(r["n_blocks"], r["bytes"], r["bad"], a.print_limit), a.out)
+    return 1 if r["bad"] else 0
 
 
 def write_report(lines: Sequence[str], out: Optional[str]):
@@ -713,11 +753,21 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     p.add_argument("--help", action="help")
     p.add_argument("-h", "--header", action="store_true", help="print the BAM header text first")
     p.add_argument("-m", "--max-split-size", type=parse_bytes, default=None)
+    p.add_argument("--verify-crc", action="store_true", help="check every BGZF block's CRC32 while loading")
+    p.add_argument("bam")
+    p.add_argument("out", nargs="?")
+    p = sub.add_parser("check-crc")
+    p.add_argument("-l", "--print-limit", type=int, default=10)
+    p.add_argument("--windows", type=int, default=1,
+                   help="byte-range windows run one after another on one GPU (files larger than HBM); "
+                        "0 = as many as the file's size, compression ratio and free HBM need")
+    p.add_argument("--device", type=int, default=None)
     p.add_argument("bam")
     p.add_argument("out", nargs="?")
     p = sub.add_parser("index-bam")
     p.add_argument("-o", "--out", default=None, help="default: BAM.bai")
     p.add_argument("--allow-unsorted", action="store_true")
+    p.add_argument("--verify-crc", action="store_true", help="check every BGZF block's CRC32 while loading")
     p.add_argument("-m", "--max-split-size", type=parse_bytes, default=None)
     p.add_argument("bam")
     for name in ("full-check", "check-bam", "check-blocks", "compute-splits", "count-reads", "index-blocks",
@@ -747,6 +797,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         return view_main(a)
     if a.cmd == "index-bam":
         return index_bam_main(a)
+    if a.cmd == "check-crc":
+        return check_crc_main(a)
     if getattr(a, "gpus", 1) > 1:
         if "WORLD_SIZE" not in os.environ:
             return spawn_ranks(a.gpus, sys.argv[1:] if argv is None else argv)

@@ -442,6 +442,49 @@ def full_check_file(path, limit: int = 10, ranges=None, reads_to_check: int = 10
     return merge_parts(parts, limit)
 
 
+def check_crc_file(path, world: int = 1, device: int = 0, split_size: int = 2 << 20, halo: int = 2 << 20) -> dict:
+    """`check-crc` over `world` byte-range windows, one after another on one context (a file larger than HBM): every
+    window scans and inflates its range and checks the CRC32 of the blocks it owns (owned_blocks, as full_check_file's
+    ungrouped branch), so every block of the file is counted once.  `path`: a file name, or a (source, file_size)
+    pair.  Returns the merged totals (n_blocks, n_bad, bytes), `bad`: the sorted (file offset, stored, computed) of the
+    mismatching blocks, and `windows`: each window's n_blocks.  Needs no BAM header, so any BGZF file serves.  Not for
+    use inside a process group."""
+    source, size = file_source(path) if isinstance(path, (str, os.PathLike)) else path
+    plans = plan_shards(size, split_size, max(1, int(world)))
+    out = {"n_blocks": 0, "n_bad": 0, "bytes": 0, "bad": [], "windows": []}
+
+    def window(f, p):
+        own = int(owned_blocks(f, p).sum())  # (the owned blocks are the table's first ones)
+        r = f.check_crc(0, own)
+        if r["n_bad"]:
+            computed, stored = f.block_crcs()
+            r["bad_values"] = [(int(o), int(stored[b]), int(computed[b])) for b, o in zip(r["bad"], r["bad_offsets"])]
+        return r
+
+    sh = None
+    try:
+        for p in plans:
+            lo, hi = p.load_range(halo)
+            if p.lo >= p.owned_hi:  # more windows than Hadoop splits: nothing to own
+                out["windows"].append(0)
+                continue
+            if sh is None:
+                sh = GpuShard(p, source, split_size, (), device=device, halo=halo)
+            else:
+                sh.halo = halo
+                sh.reload(p, source(lo, hi))
+            r = sh.run(window)
+            for k in ("n_blocks", "n_bad", "bytes"):
+                out[k] += r[k]
+            out["bad"] += r.get("bad_values", [])
+            out["windows"].append(r["n_blocks"])
+    finally:
+        if sh is not None:
+            sh.close()
+    out["bad"].sort()
+    return out
+
+
 class WindowPipe:
     """A rank's byte range streamed through two contexts in W windows (`wplans`: the windows' ShardPlans): while
     window w computes on one context, a loader thread copies window w+1's bytes into the other (sbam_load's host →
