@@ -332,6 +332,81 @@ int sbam_get_record_fields(sbam_ctx *ctx, const sbam_record_fields *out);
  * that was not selected is NULL. */
 int sbam_record_fields_device(sbam_ctx *ctx, sbam_record_fields *dev, int64_t *i0, int64_t *n);
 
+/* ---- typed tags: SAMRecord.getAttribute (SAM spec §4.2.4) -------------------------------------------------- */
+
+#define SBAM_MAX_TAGS 32
+
+/* One entry of a tag query: the two-character name, and whether the value's bytes are wanted as a CSR column. */
+typedef struct {
+  char tag[2];
+  uint8_t want_bytes;
+  uint8_t reserved;
+} sbam_tag_query;
+
+/* Columns of a batch of n records and a query of n_tags entries, tag-major: entry j, record k at index j * n + k.
+ *   type   the stored type byte, one of A c C s S i I f Z H B; 0 when the record has no such tag
+ *   sub    a B array's element type; 0 otherwise
+ *   rel    offset of the value's first byte inside the record's tag bytes (sbam_load_record_fields' aux column:
+ *          aux[aux_off[k] + rel]); Z and H: the first character; B: the first element, behind subtype and count;
+ *          -1 when absent
+ *   value  c s i sign-extended, C S I zero-extended, A the byte, f the 32 IEEE bits zero-extended, Z and H the length
+ *          in bytes without the NUL, B the element count; 0 when absent
+ * and for every entry j with want_bytes a CSR column: bytes_off[j] (n + 1 int64, exclusive prefix sums) and bytes[j],
+ * holding a Z or H value's characters without the NUL, a B array's raw little-endian element bytes, and nothing for
+ * scalar types and absent tags.  Entries of bytes_off / bytes whose query entry has no want_bytes (or j >= n_tags)
+ * are NULL. */
+typedef struct {
+  uint8_t *type;
+  uint8_t *sub;
+  int32_t *rel;
+  int64_t *value;
+  int64_t *bytes_off[SBAM_MAX_TAGS];
+  uint8_t *bytes[SBAM_MAX_TAGS];
+} sbam_record_tags;
+
+typedef struct {
+  int64_t present[SBAM_MAX_TAGS]; /* records of the batch that have the tag */
+  int64_t bytes[SBAM_MAX_TAGS];   /* the entry's CSR total (0 without want_bytes) */
+} sbam_record_tag_totals;
+
+/* Decode the tags named by q[0 .. n_tags) of records [i0, i0 + n) of the last sbam_load_records into device columns
+ * owned by ctx: what htsjdk SAMRecord.getAttribute(tag) answers for the SAMRecords BAMRecordCodec.decode builds behind
+ * RecordStream.scala:16-33, i.e. those of loadReads (CanLoadBam.scala:221-241); tag layout SAM spec §4.2.4.  The tag
+ * bytes are read straight from the inflated stream; no sbam_load_record_fields is needed.  Rules:
+ *   whole list   a record's whole tag list is always walked and validated, whatever is queried, so whether a batch is
+ *                well-formed does not depend on the query;
+ *   duplicates   the first occurrence of a tag in a record wins;
+ *   malformed    SBAM_ERR_RECORD with error.position = the stream offset of the first such record of the batch, and
+ *                nothing is produced, for: fewer than 3 bytes left for a tag header; an unknown type byte; a value
+ *                that runs past the record's end; a Z or H value with no NUL before the record's end; a B array with
+ *                an unknown subtype, a negative count, or elements past the end; and the structural failures
+ *                sbam_load_record_fields reports (a negative l_seq, fields past block_size, a record past the stream);
+ *   state        SBAM_ERR_STATE without loaded records;
+ *   arguments    SBAM_ERR_ARG for a range outside the loaded records, n_tags outside 1..SBAM_MAX_TAGS, a tag that is
+ *                not [A-Za-z][A-Za-z0-9], or the same tag twice in the query;
+ *   empty batch  n = 0 is SBAM_OK with zero totals;
+ *   lifetime     the columns live in buffers of their own (grow-only, sized by one rule) and stay valid until the next
+ *                sbam_load_record_tags, load, reset or close; a later sbam_load_record_fields does not invalidate
+ *                them, nor the reverse;
+ *   timing       sbam_last_kernel_ms(ctx, "record_tags") is the device time of the call.
+ * *totals (may be NULL) receives the per-entry counts. */
+int sbam_load_record_tags(sbam_ctx *ctx, int64_t i0, int64_t n, const sbam_tag_query *q, int32_t n_tags,
+                          sbam_record_tag_totals *totals);
+
+/* Copy the columns of the last sbam_load_record_tags into caller-owned host buffers (type, sub, rel, value: n_tags * n
+ * entries; bytes_off[j]: n + 1; bytes[j]: its total): the host form of SAMRecord.getAttribute over the batch
+ * (BAMRecordCodec.decode behind RecordStream.scala:16-33; SAM spec §4.2.4).  NULL members are not copied; a bytes_off
+ * or bytes member of an entry without want_bytes is SBAM_ERR_ARG. */
+int sbam_get_record_tags(sbam_ctx *ctx, const sbam_record_tags *out);
+
+/* Device pointers of the last sbam_load_record_tags' columns, its batch and its query size (for in-process GPU
+ * consumers; no copy; the device-side form of SAMRecord.getAttribute, SAM spec §4.2.4, CanLoadBam.scala:221-241). */
+int sbam_record_tags_device(sbam_ctx *ctx, sbam_record_tags *dev, int64_t *i0, int64_t *n, int32_t *n_tags);
+
+/* Tag bytes above which sbam_load_record_tags walks one record with a whole wave (SAM spec §4.2.4; no reference
+ * counterpart, htsjdk's BAMRecordCodec.decode is sequential): for tests that must reach that path. */
+int sbam_tag_long_aux_bytes(void);
+
 /* ---- BAI index writer (SAM spec §5.2, §5.3; the layout the reference reads in check/.../bam/index/Index.scala:53-90) -- */
 
 /* The index is built from the record columns of the last sbam_load_records, in file order, by these rules (the usual
@@ -403,7 +478,8 @@ int sbam_index_long_cigar_ops(void);
 /* Device time (ms, HIP events on the library's stream) of the most recent launch of a named kernel
  * family: "scan", "inflate", "check_full", "check_eager", "records", "load_records", "record_fields" (the gather of
  * sbam_load_record_fields; "record_field_sizes": its sizes and scan), "index" (sbam_build_index, from its first pass
- * through the linear index's fill), "crc" (the block CRC32 check). Returns -1 if none. */
+ * through the linear index's fill), "crc" (the block CRC32 check), "record_tags" (sbam_load_record_tags: its walk and
+ * scans, "record_tag_walk", plus the gather of its byte columns, "record_tag_bytes"). Returns -1 if none. */
 double sbam_last_kernel_ms(sbam_ctx *ctx, const char *kernel);
 
 #ifdef __cplusplus

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "sbam_internal.h"
+#include "sbam_tag_core.h"
 
 using namespace sbam;
 
@@ -249,6 +250,14 @@ struct sbam_ctx {
   sbam_record_fields fdev{};  // device pointers (data of unselected fields: null)
   int64_t f_i0 = 0, f_n = -1;
   sbam_record_field_totals f_tot{};
+  // typed tags of the last sbam_load_record_tags: the four cell columns; the byte columns' offsets, source positions
+  // and scan scratch; their bytes (ensure_tags / ensure_tag_bytes)
+  DevBuf<uint8_t> d_tcell, d_toff, d_tdata;
+  sbam_record_tags tdev{};  // device pointers (byte columns of entries without want_bytes: null)
+  int64_t t_i0 = 0, t_n = -1;
+  int32_t t_nq = 0;
+  bool t_bytes[SBAM_MAX_TAGS] = {};  // which query entries have a byte column
+  sbam_record_tag_totals t_tot{};
   // sbam_load_records covered every split of a whole file (what sbam_build_index needs)
   bool loaded_all = false;
   // BAI index of the last sbam_build_index: per-record scratch (end, bin), per-workgroup run heads, the counter
@@ -334,7 +343,7 @@ hipError_t drop_stages(sbam_ctx *c) {
   c->crc_b0 = c->crc_b1 = -1;
   drop_bitmap(c);
   c->n_loaded = -1;
-  c->f_n = -1;
+  c->f_n = c->t_n = -1;
   c->loaded_all = c->idx_built = false;
   return e;
 }
@@ -407,6 +416,48 @@ hipError_t ensure_index(sbam_ctx *c, size_t N, bool *grew = nullptr) {
   HIPTRY(c->d_iend.ensure(N, grew));
   HIPTRY(c->d_ibin.ensure(N, grew));
   return c->d_iheads.ensure((size_t)index_blocks((int64_t)N) + 1, grew);
+}
+
+// Typed tags of n records, nq query entries, nb of them with a byte column.  Every piece is 256-B aligned.
+//   d_tcell  type | sub | rel | value, nq * n entries each
+//   d_toff   nb offset columns of n + 1 int64 | nb source-position columns of n | the scans' per-workgroup sums |
+//            first bad record, 32 byte totals, kTagPresentSlots x 32 present counters
+constexpr size_t kTagSmallWords = 1 + SBAM_MAX_TAGS + (size_t)kTagPresentSlots * SBAM_MAX_TAGS;
+struct TagLayout {
+  size_t sub, rel, value, cell_bytes;       // offsets into d_tcell, and its size
+  size_t ostride, src, bsum, small, off_bytes;  // (ostride: bytes per offset column) offsets into d_toff, and its size
+};
+size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+TagLayout tag_layout(size_t n, size_t nq, size_t nb) {
+  TagLayout t;
+  const size_t cells = nq * n;
+  t.sub = up256(cells);
+  t.rel = t.sub + up256(cells);
+  t.value = t.rel + up256(cells * 4);
+  t.cell_bytes = t.value + up256(cells * 8);
+  t.ostride = up256((n + 1) * 8);
+  t.src = nb * t.ostride;
+  t.bsum = t.src + nb * up256(n * 8);
+  t.small = t.bsum + up256(nb * (size_t)tag_scan_blocks((int64_t)n) * 8);
+  t.off_bytes = t.small + up256(kTagSmallWords * 8);
+  return t;
+}
+hipError_t ensure_tags(sbam_ctx *c, const TagLayout &t, bool *grew = nullptr) {
+  HIPTRY(c->d_tcell.ensure(t.cell_bytes, grew));
+  return c->d_toff.ensure(t.off_bytes, grew);
+}
+// the byte columns (each padded to the gather's 8-byte stores) with the gather's per-tile record ranges behind each;
+// at[b], tiles_at[b]: column b's offsets into d_tdata
+hipError_t ensure_tag_bytes(sbam_ctx *c, const int64_t *bytes, int nb, size_t *at, size_t *tiles_at,
+                            bool *grew = nullptr) {
+  size_t need = 0;
+  for (int b = 0; b < nb; b++) {
+    at[b] = need;
+    need += up256((size_t)bytes[b] + 8);
+    tiles_at[b] = need;
+    need += up256((size_t)field_gather_tiles(bytes[b]) * 16);
+  }
+  return c->d_tdata.ensure(need, grew);
 }
 
 // Header.make details at relative offset q (for HeaderParseException).
@@ -600,6 +651,10 @@ int sbam_reset(sbam_ctx *c) {
 }
 
 double sbam_last_kernel_ms(sbam_ctx *c, const char *kernel) {
+  if (!std::strcmp(kernel, "record_tags")) {  // two spans with the host's look at the totals between them
+    const double walk = sbam_last_kernel_ms(c, "record_tag_walk"), bytes = sbam_last_kernel_ms(c, "record_tag_bytes");
+    return walk < 0 ? -1.0 : walk + (bytes < 0 ? 0.0 : bytes);
+  }
   auto it = c->ev.find(kernel);
   if (it == c->ev.end()) return -1.0;
   (void)hipEventSynchronize(it->second.second);
@@ -1400,7 +1455,7 @@ int sbam_load_records(sbam_ctx *c, const sbam_split_args *a, int64_t first, int6
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   c->n_loaded = -1;
-  c->f_n = -1;
+  c->f_n = c->t_n = -1;
   c->loaded_all = c->idx_built = false;
   std::vector<int64_t> xs, xe, cnt;
   rc = split_starts(c, a, first, count, xs, xe);
@@ -1582,6 +1637,149 @@ int sbam_record_fields_device(sbam_ctx *c, sbam_record_fields *d, int64_t *i0, i
   *d = c->fdev;
   if (i0) *i0 = c->f_i0;
   if (n) *n = c->f_n;
+  return SBAM_OK;
+}
+
+// ---- typed tags (SAM spec §4.2.4; htsjdk SAMRecord.getAttribute over BAMRecordCodec.decode's records) -------------
+int sbam_tag_long_aux_bytes(void) { return tag_long_aux_bytes(); }
+
+int sbam_load_record_tags(sbam_ctx *c, int64_t i0, int64_t n, const sbam_tag_query *q, int32_t n_tags,
+                          sbam_record_tag_totals *totals) {
+  if (!c) return SBAM_ERR_ARG;
+  if (c->n_loaded < 0 || c->L < 0) return set_err(c, SBAM_ERR_STATE, "sbam_load_records has not run");
+  if (i0 < 0 || n < 0 || i0 + n > c->n_loaded)
+    return set_err(c, SBAM_ERR_ARG, "records [%lld, %lld) outside the %lld loaded", (long long)i0, (long long)(i0 + n),
+                   (long long)c->n_loaded);
+  if (!q || n_tags < 1 || n_tags > SBAM_MAX_TAGS) return set_err(c, SBAM_ERR_ARG, "%d tags in the query", (int)n_tags);
+  TagWalkArgs wa{};
+  int nb = 0;
+  for (int j = 0; j < n_tags; j++) {
+    const unsigned char a = (unsigned char)q[j].tag[0], b = (unsigned char)q[j].tag[1];
+    const bool alpha = (a >= 'A' && a <= 'Z') || (a >= 'a' && a <= 'z');
+    const bool alnum = (b >= 'A' && b <= 'Z') || (b >= 'a' && b <= 'z') || (b >= '0' && b <= '9');
+    if (!alpha || !alnum)
+      return set_err(c, SBAM_ERR_ARG, "query entry %d is not a tag name [A-Za-z][A-Za-z0-9]", j);
+    wa.key[j] = (uint16_t)(a | (b << 8));
+    for (int i = 0; i < j; i++)
+      if (wa.key[i] == wa.key[j]) return set_err(c, SBAM_ERR_ARG, "tag %c%c twice in the query", a, b);
+    wa.bcol[j] = q[j].want_bytes ? (int8_t)nb++ : (int8_t)-1;
+    wa.filter |= 1ull << sbam_tag::filter_bit(wa.key[j]);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  c->t_n = -1;
+  c->tdev = sbam_record_tags{};
+  c->t_tot = sbam_record_tag_totals{};
+  if (totals) *totals = c->t_tot;
+  c->t_nq = n_tags;
+  for (int j = 0; j < SBAM_MAX_TAGS; j++) c->t_bytes[j] = j < n_tags && wa.bcol[j] >= 0;
+  if (n == 0) {
+    c->t_i0 = i0;
+    c->t_n = 0;
+    return SBAM_OK;
+  }
+  const TagLayout lay = tag_layout((size_t)n, (size_t)n_tags, (size_t)nb);
+  HIPCHK(c, ensure_tags(c, lay));
+  const RecordColumnsDev &k = c->rcols;
+  uint8_t *cell = c->d_tcell, *ob = c->d_toff;
+  int64_t *small = reinterpret_cast<int64_t *>(ob + lay.small);  // [0] bad, [1 ..] byte totals, [1 + 32 ..] present slots
+  wa.rec = FieldSizesArgs{c->d_roff + i0, k.block_size + i0, k.bin_mq_nl + i0, k.flag_nc + i0, k.l_seq + i0, n, c->L};
+  wa.u = c->d_u;
+  wa.nq = n_tags;
+  wa.nb = nb;
+  wa.type = cell;
+  wa.sub = cell + lay.sub;
+  wa.rel = reinterpret_cast<int32_t *>(cell + lay.rel);
+  wa.value = reinterpret_cast<int64_t *>(cell + lay.value);
+  wa.off = reinterpret_cast<int64_t *>(ob);
+  wa.ostride = (int64_t)(lay.ostride / 8);
+  wa.src = reinterpret_cast<int64_t *>(ob + lay.src);
+  wa.first_bad = reinterpret_cast<unsigned long long *>(small);
+  wa.present = wa.first_bad + 1 + SBAM_MAX_TAGS;
+  {
+    Timer t(c, "record_tag_walk");
+    HIPCHK(c, hipMemsetAsync(small, 0, kTagSmallWords * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(small, 0xff, 8, c->stream));
+    HIPCHK(c, launch_tag_walk(wa, c->stream));
+    HIPCHK(c, launch_tag_scan(wa.off, wa.ostride, n, nb, reinterpret_cast<int64_t *>(ob + lay.bsum),
+                              small + 1, c->stream));
+  }
+  std::vector<int64_t> h(kTagSmallWords);
+  HIPCHK(c, hipMemcpyAsync(h.data(), small, kTagSmallWords * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (h[0] != -1) {  // nothing is produced; the gather is not launched
+    int64_t x = -1;
+    HIPCHK(c, hipMemcpy(&x, c->d_roff + i0 + h[0], 8, hipMemcpyDeviceToHost));
+    c->err.position = x;
+    return set_err(c, SBAM_ERR_RECORD, "record %lld at %lld: malformed tag list, or variable-length fields overrun block_size",
+                   (long long)(i0 + h[0]), (long long)x);
+  }
+  sbam_record_tag_totals tot{};
+  int64_t col_bytes[SBAM_MAX_TAGS];
+  for (int j = 0; j < n_tags; j++) {
+    for (int s = 0; s < kTagPresentSlots; s++) tot.present[j] += h[1 + SBAM_MAX_TAGS + s * SBAM_MAX_TAGS + j];
+    if (wa.bcol[j] >= 0) tot.bytes[j] = col_bytes[wa.bcol[j]] = h[1 + wa.bcol[j]];
+  }
+  size_t at[SBAM_MAX_TAGS], tiles_at[SBAM_MAX_TAGS];
+  HIPCHK(c, ensure_tag_bytes(c, col_bytes, nb, at, tiles_at));
+  sbam_record_tags dev{wa.type, wa.sub, wa.rel, wa.value, {}, {}};
+  {
+    Timer t(c, "record_tag_bytes");
+    for (int j = 0; j < n_tags; j++) {
+      const int b = wa.bcol[j];
+      if (b < 0) continue;
+      dev.bytes_off[j] = wa.off + b * wa.ostride;
+      dev.bytes[j] = c->d_tdata + at[b];
+      FieldGatherArgs ga{c->d_u, nullptr, nullptr, nullptr, nullptr, dev.bytes_off[j], n, 0, col_bytes[b], dev.bytes[j],
+                         reinterpret_cast<int64_t *>(c->d_tdata + tiles_at[b])};
+      ga.src = wa.src + b * n;
+      HIPCHK(c, launch_field_gather(5, ga, c->stream));
+    }
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->tdev = dev;
+  c->t_tot = tot;
+  c->t_i0 = i0;
+  c->t_n = n;
+  if (totals) *totals = tot;
+  return SBAM_OK;
+}
+
+int sbam_get_record_tags(sbam_ctx *c, const sbam_record_tags *o) {
+  if (!c || !o) return SBAM_ERR_ARG;
+  if (c->t_n < 0) return set_err(c, SBAM_ERR_STATE, "sbam_load_record_tags has not run");
+  for (int j = 0; j < SBAM_MAX_TAGS; j++)
+    if ((o->bytes_off[j] || o->bytes[j]) && !c->t_bytes[j])
+      return set_err(c, SBAM_ERR_ARG, "the bytes of query entry %d were not asked of sbam_load_record_tags", j);
+  if (c->t_n == 0) {  // an empty batch: each offset column is its single 0
+    for (int j = 0; j < SBAM_MAX_TAGS; j++)
+      if (o->bytes_off[j]) *o->bytes_off[j] = 0;
+    return SBAM_OK;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const sbam_record_tags &d = c->tdev;
+  const size_t cells = (size_t)c->t_nq * (size_t)c->t_n;
+  auto copy = [&](void *dst, const void *src, size_t bytes) {
+    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+  };
+  HIPCHK(c, copy(o->type, d.type, cells));
+  HIPCHK(c, copy(o->sub, d.sub, cells));
+  HIPCHK(c, copy(o->rel, d.rel, cells * 4));
+  HIPCHK(c, copy(o->value, d.value, cells * 8));
+  for (int j = 0; j < c->t_nq; j++) {
+    HIPCHK(c, copy(o->bytes_off[j], d.bytes_off[j], (size_t)(c->t_n + 1) * 8));
+    HIPCHK(c, copy(o->bytes[j], d.bytes[j], (size_t)c->t_tot.bytes[j]));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SBAM_OK;
+}
+
+int sbam_record_tags_device(sbam_ctx *c, sbam_record_tags *d, int64_t *i0, int64_t *n, int32_t *n_tags) {
+  if (!c || !d) return SBAM_ERR_ARG;
+  if (c->t_n < 0) return set_err(c, SBAM_ERR_STATE, "sbam_load_record_tags has not run");
+  *d = c->t_n ? c->tdev : sbam_record_tags{};  // (an empty batch has no columns)
+  if (i0) *i0 = c->t_i0;
+  if (n) *n = c->t_n;
+  if (n_tags) *n_tags = c->t_nq;
   return SBAM_OK;
 }
 

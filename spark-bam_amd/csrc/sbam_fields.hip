@@ -39,25 +39,6 @@ constexpr int kStepBytes = kGatherThreads * kLaneBytes;  // 2 KiB of one output 
 constexpr int field_steps(int field) { return field == 1 ? 2 : 4; }
 constexpr int kStageCap = 1040;      // a tile's records kept in LDS (more: searched in global memory)
 
-// lengths of record k's four CSR columns; a record that fails validation has none
-struct FieldLens {
-  int64_t v[4];  // name bytes, cigar ops, bases, aux bytes
-  bool bad;
-};
-
-SB_DEV FieldLens field_lens(const FieldSizesArgs &a, int64_t k) {
-  FieldLens r;
-  const int64_t bs = a.block_size[k], ls = a.l_seq[k];
-  const int64_t lrn = a.bin_mq_nl[k] & 0xffu, nc = a.flag_nc[k] & 0xffffu;
-  const int64_t need = 36 + lrn + 4 * nc + ((ls + 1) >> 1) + ls;
-  r.bad = ls < 0 || need > 4 + bs || a.roff[k] + 4 + bs > a.L;
-  r.v[0] = r.bad ? 0 : (lrn > 1 ? lrn - 1 : 0);
-  r.v[1] = r.bad ? 0 : nc;
-  r.v[2] = r.bad ? 0 : ls;
-  r.v[3] = r.bad ? 0 : 4 + bs - need;
-  return r;
-}
-
 // inclusive scan of four int64 per thread across the workgroup; total[f] = the workgroup's sum
 SB_DEV void block_scan4(const int64_t v[4], int64_t incl[4], int64_t total[4], int64_t (*ws)[4]) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -170,11 +151,13 @@ SB_DEV uint64_t bases8(const uint8_t *u, int64_t x, int64_t b) {
   return (uint64_t)bases4(h & 0xffffu) | ((uint64_t)bases4(h >> 16) << 32);
 }
 
-enum : int { F_NAME = 0, F_CIGAR = 1, F_SEQ = 2, F_QUAL = 3, F_AUX = 4 };
+enum : int { F_NAME = 0, F_CIGAR = 1, F_SEQ = 2, F_QUAL = 3, F_AUX = 4, F_AT = 5 };
 
-// stream offset of record r's field F (SAM spec §4.2: 36 fixed bytes, read_name, cigar, seq, qual, tags)
+// stream offset of record r's field F (SAM spec §4.2: 36 fixed bytes, read_name, cigar, seq, qual, tags); F_AT: the
+// position column a.src gives (a tag's value, sbam_tags.hip)
 template <int F>
 SB_DEV int64_t field_start(const FieldGatherArgs &a, int64_t r) {
+  if (F == F_AT) return a.src[r];
   int64_t x = a.roff[r] + 36;
   if (F == F_NAME) return x;
   x += a.bin_mq_nl[r] & 0xffu;
@@ -300,6 +283,7 @@ hipError_t launch_field_gather(int field, const FieldGatherArgs &a, hipStream_t 
     case F_SEQ: return gather<F_SEQ>(a, s);
     case F_QUAL: return gather<F_QUAL>(a, s);
     case F_AUX: return gather<F_AUX>(a, s);
+    case F_AT: return gather<F_AT>(a, s);
   }
   return hipErrorInvalidValue;
 }

@@ -184,6 +184,23 @@ struct FieldSizesArgs {
   const int32_t *l_seq;
   int64_t n, L;
 };
+// lengths of record k's four CSR columns; a record that fails validation has none
+struct FieldLens {
+  int64_t v[4];  // name bytes, cigar ops, bases, aux bytes
+  bool bad;
+};
+__device__ __forceinline__ FieldLens field_lens(const FieldSizesArgs &a, int64_t k) {
+  FieldLens r;
+  const int64_t bs = a.block_size[k], ls = a.l_seq[k];
+  const int64_t lrn = a.bin_mq_nl[k] & 0xffu, nc = a.flag_nc[k] & 0xffffu;
+  const int64_t need = 36 + lrn + 4 * nc + ((ls + 1) >> 1) + ls;
+  r.bad = ls < 0 || need > 4 + bs || a.roff[k] + 4 + bs > a.L;
+  r.v[0] = r.bad ? 0 : (lrn > 1 ? lrn - 1 : 0);
+  r.v[1] = r.bad ? 0 : nc;
+  r.v[2] = r.bad ? 0 : ls;
+  r.v[3] = r.bad ? 0 : 4 + bs - need;
+  return r;
+}
 struct FieldOffsets {  // n + 1 int64 each
   int64_t *name, *cigar, *seq, *aux;
 };
@@ -198,13 +215,15 @@ struct FieldGatherArgs {
   int64_t total;       // output bytes
   uint8_t *out;        // 8-byte aligned, room for total rounded up to 8
   int64_t *tiles;      // scratch: 2 * field_gather_tiles(total) int64 (each tile's first and last record)
+  const int64_t *src = nullptr;  // field 5 only: each record's source position in the stream
 };
 int64_t field_size_blocks(int64_t n);  // entries per length of launch_field_sizes' bsum scratch
 int64_t field_gather_tiles(int64_t total);
 // lengths, validation (first_bad = min failing record index of the batch, ~0 when none) and offsets; totals[4]
 hipError_t launch_field_sizes(const FieldSizesArgs &a, int64_t *bsum, FieldOffsets off, unsigned long long *first_bad,
                               int64_t *totals, hipStream_t s);
-// field: 0 name, 1 cigar, 2 seq (ASCII bases), 3 qual, 4 aux
+// field: 0 name, 1 cigar, 2 seq (ASCII bases), 3 qual, 4 aux, 5 the bytes at a.src[r] (roff and the fixed-field
+// columns are then not read)
 hipError_t launch_field_gather(int field, const FieldGatherArgs &a, hipStream_t s);
 // BAI index from the record columns (sbam_index.hip).  Records in file order; the block table as for
 // launch_record_columns (+ csize: the address behind the last block is where the last record ends).
@@ -240,5 +259,31 @@ hipError_t launch_index_pass1(const IndexArgs &a, IndexStats st, int64_t *heads,
 // its backward fill
 hipError_t launch_index_pass2(const IndexArgs &a, const int64_t *heads, IndexRuns r, const int64_t *intv_off,
                               unsigned long long *ioffset, hipStream_t s);
+
+// Typed tags of decoded records (sbam_tags.hip): the walk over records [0, n) of a batch, the scans of the byte
+// columns' lengths, and (through launch_field_gather, field 5) their bytes.
+struct TagWalkArgs {
+  FieldSizesArgs rec;            // the batch's fixed-field columns
+  const uint8_t *u;              // the stream (rec.L bytes and its pad)
+  int32_t nq, nb;                // queried tags; byte columns
+  uint16_t key[32];              // name[0] | name[1] << 8 per query entry
+  int8_t bcol[32];               // the entry's byte column, -1: none
+  unsigned long long filter;     // sbam_tag::filter_bit of every key
+  uint8_t *type, *sub;           // nq * n each, tag-major
+  int32_t *rel;
+  int64_t *value;
+  int64_t *off;                  // byte column b's lengths at off[b * ostride + k] (scanned in place afterwards)
+  int64_t ostride;
+  int64_t *src;                  // and its values' stream positions at src[b * n + k]
+  unsigned long long *first_bad; // min index of a malformed record (preset ~0)
+  unsigned long long *present;   // kTagPresentSlots x 32 counters (preset 0): entry j's count is the sum over slots
+};
+constexpr int kTagPresentSlots = 64;
+int tag_long_aux_bytes();
+int64_t tag_scan_blocks(int64_t n);  // entries per byte column of launch_tag_scan's bsum scratch
+hipError_t launch_tag_walk(const TagWalkArgs &a, hipStream_t s);
+// off[b * ostride + k], k < n: lengths -> exclusive prefix sums, [n] = totals[b] = the column's bytes
+hipError_t launch_tag_scan(int64_t *off, int64_t ostride, int64_t n, int32_t nb, int64_t *bsum, int64_t *totals,
+                           hipStream_t s);
 
 }  // namespace sbam

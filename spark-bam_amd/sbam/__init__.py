@@ -84,8 +84,10 @@ class HaloException(SbamError):
 
 
 class RecordFieldsException(SbamError):
-    """A record whose variable-length fields overrun its block_size (sbam_load_record_fields)."""
+    """A record whose variable-length fields overrun its block_size (sbam_load_record_fields) or whose tag list is
+    malformed (sbam_load_record_tags); `position` is the record's stream offset."""
     code = ERR_RECORD
+    position = None
 
 
 class CrcException(IOError, SbamError):
@@ -144,6 +146,22 @@ class _RecordFieldTotals(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int64) for n in ("name_bytes", "cigar_ops", "seq_bases", "aux_bytes")]
 
 
+MAX_TAGS = 32  # SBAM_MAX_TAGS
+
+
+class _TagQuery(ctypes.Structure):
+    _fields_ = [("tag", ctypes.c_char * 2), ("want_bytes", ctypes.c_uint8), ("reserved", ctypes.c_uint8)]
+
+
+class _RecordTags(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("type", "sub", "rel", "value")] + \
+        [("bytes_off", ctypes.c_void_p * MAX_TAGS), ("bytes", ctypes.c_void_p * MAX_TAGS)]
+
+
+class _RecordTagTotals(ctypes.Structure):
+    _fields_ = [("present", ctypes.c_int64 * MAX_TAGS), ("bytes", ctypes.c_int64 * MAX_TAGS)]
+
+
 class _IndexTotals(ctypes.Structure):
     _fields_ = [("n_ref", ctypes.c_int32), ("reserved", ctypes.c_int32)] + \
         [(n, ctypes.c_int64) for n in ("n_runs", "n_intv_total", "n_no_coor", "n_unsorted", "n_records")]
@@ -176,6 +194,32 @@ class RecordFields:
     qual: Optional[np.ndarray] = None
     aux_off: Optional[np.ndarray] = None
     aux: Optional[np.ndarray] = None
+
+
+@dataclass
+class RecordTags:
+    """Typed tags of records [i0, i0 + n) (sbam_load_record_tags): `type`, `sub`, `rel`, `value` are [len(tags), n]
+    arrays (None with host=False); `bytes_off[tag]` (int64[n + 1]) and `bytes[tag]` (uint8) exist for the tags of
+    `bytes_for`; `totals[tag]` = {"present", "bytes"}."""
+    i0: int
+    n: int
+    tags: tuple
+    totals: dict
+    type: Optional[np.ndarray] = None
+    sub: Optional[np.ndarray] = None
+    rel: Optional[np.ndarray] = None
+    value: Optional[np.ndarray] = None
+    bytes_off: Optional[dict] = None
+    bytes: Optional[dict] = None
+
+    def floats(self, tag: str) -> np.ndarray:
+        """The float32 view of the low 32 bits of a tag's values (meaningful where its type is `f`)."""
+        return (self.value[self.tags.index(tag)] & 0xffffffff).astype(np.uint32).view(np.float32)
+
+    def texts(self, tag: str) -> list:
+        """A tag's value bytes per record (`bytes`), None where the record has no such tag; needs `bytes_for`."""
+        j, off, data = self.tags.index(tag), self.bytes_off[tag].tolist(), self.bytes[tag].tobytes()
+        return [data[off[k]:off[k + 1]] if t else None for k, t in enumerate(self.type[j].tolist())]
 
 
 _vp, _i64, _i32, _P = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER
@@ -216,6 +260,10 @@ _SIGNATURES = {  # (restype, argtypes) of every symbol include/sbam.h declares
     "sbam_load_record_fields": (ctypes.c_int, [_vp, _i64, _i64, ctypes.c_uint32, _P(_RecordFieldTotals)]),
     "sbam_get_record_fields": (ctypes.c_int, [_vp, _P(_RecordFields)]),
     "sbam_record_fields_device": (ctypes.c_int, [_vp, _P(_RecordFields), _P(_i64), _P(_i64)]),
+    "sbam_load_record_tags": (ctypes.c_int, [_vp, _i64, _i64, _P(_TagQuery), _i32, _P(_RecordTagTotals)]),
+    "sbam_get_record_tags": (ctypes.c_int, [_vp, _P(_RecordTags)]),
+    "sbam_record_tags_device": (ctypes.c_int, [_vp, _P(_RecordTags), _P(_i64), _P(_i64), _P(_i32)]),
+    "sbam_tag_long_aux_bytes": (ctypes.c_int, []),
     "sbam_build_index": (ctypes.c_int, [_vp, _P(_IndexTotals)]),
     "sbam_get_index_runs": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sbam_get_index_refs": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -442,6 +490,8 @@ class BamFile:
         exc = _EXC.get(rc, SbamError)(msg)
         if rc == ERR_CRC and e:
             exc.position, exc.expected, exc.actual = int(e.position), int(e.expected), int(e.actual)
+        if rc == ERR_RECORD and e:
+            exc.position = int(e.position)
         raise exc
 
     def close(self):
@@ -797,6 +847,46 @@ class BamFile:
             ptrs[f] = a.ctypes.data if a.size else None
         rf = _RecordFields(**ptrs)
         self._check(self.L.sbam_get_record_fields(self.ctx, ctypes.byref(rf)))
+        return out
+
+    def load_record_tags(self, tags: Sequence[str], i0: int = 0, n: Optional[int] = None,
+                         bytes_for: Sequence[str] = (), host: bool = True) -> RecordTags:
+        """The tags named in `tags` of records [i0, i0 + n) of the last load_records as typed columns, decoded on the
+        GPU from the inflated stream (sbam_load_record_tags: htsjdk's SAMRecord.getAttribute over loadReads' records,
+        CanLoadBam.scala:221-241; SAM spec §4.2.4).  `bytes_for`: the tags whose value bytes (Z and H characters, B
+        elements) are wanted as CSR columns.  `n=None`: through the last loaded record.  With host=False only the
+        totals are filled and the columns stay on the device (sbam_record_tags_device)."""
+        tags = tuple(tags)
+        if n is None:
+            n = max(self.n_loaded - i0, 0)
+        for t in list(tags) + list(bytes_for):
+            if not isinstance(t, str) or len(t.encode("latin-1", "replace")) != 2:
+                raise ValueError(f"not a two-character tag name: {t!r}")
+        if not set(bytes_for) <= set(tags):
+            raise ValueError(f"bytes_for names tags that are not queried: {sorted(set(bytes_for) - set(tags))}")
+        q = (_TagQuery * max(len(tags), 1))()
+        for j, t in enumerate(tags):
+            q[j].tag = t.encode("latin-1", "replace")
+            q[j].want_bytes = 1 if t in bytes_for else 0
+        tot = _RecordTagTotals()
+        self._check(self.L.sbam_load_record_tags(self.ctx, int(i0), int(n), q, len(tags), ctypes.byref(tot)))
+        totals = {t: {"present": int(tot.present[j]), "bytes": int(tot.bytes[j])} for j, t in enumerate(tags)}
+        out = RecordTags(int(i0), int(n), tags, totals)
+        if not host:
+            return out
+        shape = (len(tags), n)
+        out.type, out.sub = np.zeros(shape, np.uint8), np.zeros(shape, np.uint8)
+        out.rel, out.value = np.zeros(shape, np.int32), np.zeros(shape, np.int64)
+        out.bytes_off, out.bytes = {}, {}
+        rt = _RecordTags(type=out.type.ctypes.data, sub=out.sub.ctypes.data, rel=out.rel.ctypes.data,
+                         value=out.value.ctypes.data)
+        for j, t in enumerate(tags):
+            if t in bytes_for:
+                out.bytes_off[t] = np.zeros(n + 1, np.int64)
+                out.bytes[t] = np.zeros(totals[t]["bytes"], np.uint8)
+                rt.bytes_off[j] = out.bytes_off[t].ctypes.data
+                rt.bytes[j] = out.bytes[t].ctypes.data if out.bytes[t].size else None
+        self._check(self.L.sbam_get_record_tags(self.ctx, ctypes.byref(rt)))
         return out
 
     # ---- BAI writer

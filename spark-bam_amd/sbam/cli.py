@@ -9,6 +9,7 @@
     python -m sbam.cli compute-splits [-s] [-l LIMIT] [-m SPLIT] BAM [OUT]
     python -m sbam.cli count-reads [-m SPLIT] BAM [OUT]
     python -m sbam.cli view [-h] [-m SPLIT] [--verify-crc] BAM [OUT]
+    python -m sbam.cli tags -t NM,RG,MD [-m SPLIT] [--verify-crc] BAM [OUT]
     python -m sbam.cli index-bam [-o OUT] [--allow-unsorted] [--verify-crc] [-m SPLIT] BAM
     python -m sbam.cli check-crc [-l LIMIT] [--windows W] BAM [OUT]
 
@@ -25,6 +26,9 @@ verbatim (tests/test_cli.py):
   * count-reads: compare/CountReads.scala:80-100, spark-bam side only;
   * view: the records of loadReads (CanLoadBam.scala:348-352) as SAM text (sbam.sam; pinned by the reference's 2.sam
     and 5k.sam), decoded on the GPU by sbam_load_record_fields.
+  * tags: one line per record of loadReads: the read name, then each requested tag as SAM prints its `type:value`
+    (htsjdk SAMRecord.getAttribute; `*` when the record has no such tag), tab-separated, the tags decoded on the GPU
+    by sbam_load_record_tags.
   * index-bam: the `.bai` sidecar (SAM spec §5.2; what `samtools index` writes and the reference's
     check/.../bam/index/Index.scala:53-90 reads), built on the GPU by sbam_build_index.
   * check-crc: every BGZF block's CRC32 against its footer (no reference counterpart: Stream.scala:49-54 never reads
@@ -687,6 +691,48 @@ def view_main(a) -> int:
     return 0
 
 
+def tags_lines(f: sbam.BamFile, tags: Sequence[str], split_size: int, batch: int = VIEW_BATCH):
+    """`name<TAB>type:value…` per record of all partitions in order: names from sbam_load_record_fields, the tags from
+    sbam_load_record_tags (both columns of one batch are alive at once), with bytes for the tags that turn out to be
+    string- or array-typed in the batch; text from sbam.sam.tag_value_text."""
+    from sbam import sam
+    f.load_records(split_size, columns=None)
+    n = f.n_loaded
+    for i0 in range(0, n, batch):
+        k = min(batch, n - i0)
+        rf = f.load_record_fields(i0, k, fields=("name",))
+        rt = f.load_record_tags(tags, i0, k)
+        need = [t for j, t in enumerate(tags) if np.isin(rt.type[j], (ord("Z"), ord("H"), ord("B"))).any()]
+        if need:
+            rt = f.load_record_tags(tags, i0, k, bytes_for=need)
+        names, no = rf.name.tobytes(), rf.name_off.tolist()
+        cols = []
+        for j, t in enumerate(tags):
+            raw = rt.texts(t) if t in need else None
+            ty, sub, val = rt.type[j].tolist(), rt.sub[j].tolist(), rt.value[j].tolist()
+            cols.append([sam.tag_value_text(chr(ty[r]), chr(sub[r]), val[r], raw[r] if raw else b"") if ty[r] else "*"
+                         for r in range(k)])
+        for r in range(k):
+            yield "\t".join([names[no[r]:no[r + 1]].decode("latin-1")] + [c[r] for c in cols])
+
+
+def tags_main(a) -> int:
+    data = open(a.bam, "rb").read()
+    tags = [t for t in a.tags.split(",") if t]
+    out = open(a.out, "wb") if a.out else sys.stdout.buffer
+    try:
+        with sbam.BamFile(data, path=a.bam, verify_crc=a.verify_crc) as f:
+            for ln in tags_lines(f, tags, sbam.effective_split_size(a.max_split_size)):
+                out.write(ln.encode("latin-1") + b"\n")
+    except sbam.CrcException as e:
+        sys.stderr.write(f"{a.bam}: {e}\n")
+        return 1
+    finally:
+        if a.out:
+            out.close()
+    return 0
+
+
 def index_bam_main(a) -> int:
     """BAM.bai (or -o OUT) from BamFile.build_bai.  A file whose records are out of coordinate order is refused, as
     samtools refuses it, unless --allow-unsorted: exit status 1, `unsorted positions` on stderr, nothing written."""
@@ -756,6 +802,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     p.add_argument("--verify-crc", action="store_true", help="check every BGZF block's CRC32 while loading")
     p.add_argument("bam")
     p.add_argument("out", nargs="?")
+    p = sub.add_parser("tags")
+    p.add_argument("-t", "--tags", required=True, help="comma-separated tag names, e.g. NM,RG,MD")
+    p.add_argument("-m", "--max-split-size", type=parse_bytes, default=None)
+    p.add_argument("--verify-crc", action="store_true", help="check every BGZF block's CRC32 while loading")
+    p.add_argument("bam")
+    p.add_argument("out", nargs="?")
     p = sub.add_parser("check-crc")
     p.add_argument("-l", "--print-limit", type=int, default=10)
     p.add_argument("--windows", type=int, default=1,
@@ -795,6 +847,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     a = ap.parse_args(argv)
     if a.cmd == "view":
         return view_main(a)
+    if a.cmd == "tags":
+        return tags_main(a)
     if a.cmd == "index-bam":
         return index_bam_main(a)
     if a.cmd == "check-crc":

@@ -11,6 +11,9 @@ loadBam with): tests/test_sam_text.py.  Rules (SAM spec §1.4, §1.5, §4.2):
 * tags keep file order; the integer types c C s S i I all print as `i`; A, Z and H print as stored; B prints as
   `B:<t>,v,v…`; f prints in Python's shortest round-trip form.  No reference fixture has an `f` or a `B` tag: the
   text of those two is parity unpinned.
+
+`find_tags` states the rules of `BamFile.load_record_tags` (sbam_load_record_tags) for one record's tag bytes, and
+`tag_value_text` renders one decoded tag; `tag_texts` is built from the same walk and the same formatting.
 """
 from __future__ import annotations
 
@@ -28,45 +31,95 @@ def _float_text(v: float) -> str:
     return str(np.float32(v))
 
 
-def tag_texts(aux: bytes) -> List[str]:
-    """`TG:t:value` for each tag of one record's raw tag bytes (SAM spec §4.2.4), in file order."""
-    out, p, n = [], 0, len(aux)
+def _array_text(st: str, raw: bytes) -> str:
+    """`B:<t>,v,v…` of a B array's element bytes."""
+    if st == "f":
+        vals = [_float_text(v) for v in struct.unpack(f"<{len(raw) // 4}f", raw)]
+    else:
+        fmt, w = _INT_TAGS[st]
+        vals = [str(v) for v in struct.unpack(f"<{len(raw) // w}{fmt[1]}", raw)]
+    return f"B:{st}" + "".join("," + v for v in vals)
+
+
+def tag_value_text(type_: str, sub: str, value: int, raw: bytes = b"") -> str:
+    """`t:value` of one decoded tag as SAM prints it (`i:3`, `Z:grp1`, `A:U`, `f:1.5`, `B:c,1,2,3`), from what
+    find_tags and the columns of load_record_tags give: the stored type, a B array's subtype, the value column's
+    entry, and the value's bytes (needed for Z, H and B)."""
+    if type_ in _INT_TAGS:
+        return f"i:{int(value)}"
+    if type_ == "A":
+        return f"A:{chr(int(value))}"
+    if type_ == "f":
+        return "f:" + _float_text(struct.unpack("<f", struct.pack("<I", int(value) & 0xffffffff))[0])
+    if type_ in "ZH":
+        return f"{type_}:{bytes(raw).decode('latin-1')}"
+    if type_ == "B":
+        return _array_text(sub, bytes(raw))
+    raise ValueError(f"unknown tag type {type_!r}")
+
+
+_SCALAR_WIDTH = {"A": 1, "c": 1, "C": 1, "s": 2, "S": 2, "i": 4, "I": 4, "f": 4}
+
+
+def _walk_tags(aux: bytes):
+    """(name, type, sub, rel, value, raw) of every tag of one record's raw tag bytes (SAM spec §4.2.4), in file order;
+    ValueError for a malformed list.  `rel` is the offset of the value's first byte (B: of its first element), `value`
+    what the value column of sbam_load_record_tags holds, `raw` the bytes of a Z, H or B value (else empty)."""
+    p, n = 0, len(aux)
     while p < n:
-        if p + 3 > n:
-            raise ValueError(f"truncated tag at byte {p} of {n}")
-        tag, t = aux[p:p + 2].decode("latin-1"), chr(aux[p + 2])
-        p += 3
-        if t in _INT_TAGS:
-            fmt, w = _INT_TAGS[t]
-            out.append(f"{tag}:i:{struct.unpack_from(fmt, aux, p)[0]}")
-            p += w
-        elif t == "A":
-            out.append(f"{tag}:A:{chr(aux[p])}")
-            p += 1
-        elif t == "f":
-            out.append(f"{tag}:f:{_float_text(struct.unpack_from('<f', aux, p)[0])}")
-            p += 4
+        if n - p < 3:
+            raise ValueError(f"truncated tag header at byte {p} of {n}")
+        name, t = aux[p:p + 2], chr(aux[p + 2])
+        left = n - p
+        if t in _SCALAR_WIDTH:
+            w = _SCALAR_WIDTH[t]
+            if 3 + w > left:
+                raise ValueError(f"value of tag at byte {p} runs past the record's end")
+            raw4 = aux[p + 3:p + 3 + w]
+            if t in _INT_TAGS:
+                v = struct.unpack(_INT_TAGS[t][0], raw4)[0]
+            else:  # A: the byte; f: the 32 IEEE bits
+                v = int.from_bytes(raw4, "little")
+            yield name, t, "", p + 3, v, b""
+            p += 3 + w
         elif t in "ZH":
-            e = aux.index(b"\0", p)
-            out.append(f"{tag}:{t}:{aux[p:e].decode('latin-1')}")
+            e = aux.find(b"\0", p + 3)
+            if e < 0:
+                raise ValueError(f"{t} value at byte {p} has no NUL before the record's end")
+            yield name, t, "", p + 3, e - p - 3, aux[p + 3:e]
             p = e + 1
         elif t == "B":
-            st = chr(aux[p])
-            cnt = struct.unpack_from("<i", aux, p + 1)[0]
-            p += 5
-            if st == "f":
-                vals = [_float_text(v) for v in struct.unpack_from(f"<{cnt}f", aux, p)]
-                w = 4
-            elif st in _INT_TAGS:
-                fmt, w = _INT_TAGS[st]
-                vals = [str(v) for v in struct.unpack_from(f"<{cnt}{fmt[1]}", aux, p)]
-            else:
-                raise ValueError(f"unknown B subtype {st!r} in tag {tag}")
-            out.append(f"{tag}:B:{st}" + "".join("," + v for v in vals))
-            p += cnt * w
+            if left < 8:
+                raise ValueError(f"B header at byte {p} runs past the record's end")
+            st = chr(aux[p + 3])
+            cnt = struct.unpack_from("<i", aux, p + 4)[0]
+            if st not in _SCALAR_WIDTH or st == "A":
+                raise ValueError(f"unknown B subtype {st!r} at byte {p}")
+            w = _SCALAR_WIDTH[st]
+            if cnt < 0 or 8 + cnt * w > left:
+                raise ValueError(f"B array at byte {p}: count {cnt} is negative or runs past the record's end")
+            yield name, t, st, p + 8, cnt, aux[p + 8:p + 8 + cnt * w]
+            p += 8 + cnt * w
         else:
-            raise ValueError(f"unknown tag type {t!r} in tag {tag}")
-    return out
+            raise ValueError(f"unknown tag type {t!r} at byte {p}")
+
+
+def find_tags(aux: bytes, tags) -> list:
+    """The host statement of sbam_load_record_tags' rules for one record: per queried two-character tag name, None
+    when the record has no such tag, else (type, sub, rel, value, raw_bytes) of its first occurrence.  The whole list
+    is walked whatever is queried; ValueError for every malformed case (fewer than 3 bytes for a header, an unknown
+    type, a value past the end, a Z or H without a NUL, a B with an unknown subtype, a negative count or elements
+    past the end).  The tests' oracle; not on the data path."""
+    want = [t.encode("latin-1") if isinstance(t, str) else bytes(t) for t in tags]
+    first = {}
+    for name, t, st, rel, v, raw in _walk_tags(bytes(aux)):
+        first.setdefault(name, (t, st, rel, v, raw))
+    return [first.get(w) for w in want]
+
+
+def tag_texts(aux: bytes) -> List[str]:
+    """`TG:t:value` for each tag of one record's raw tag bytes (SAM spec §4.2.4), in file order."""
+    return [f"{name.decode('latin-1')}:{tag_value_text(t, st, v, raw)}" for name, t, st, _, v, raw in _walk_tags(aux)]
 
 
 def cigar_text(ops: np.ndarray) -> str:
