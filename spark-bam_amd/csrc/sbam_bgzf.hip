@@ -293,6 +293,10 @@ __global__ void k_find_block_starts(const Candidate *__restrict__ c, int64_t n, 
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= nq) return;
   const int64_t s = starts[t];
+  if (nchk == 0) {  // take(0) parses no header, so the first probe is accepted (FindBlockStart.scala:19-24)
+    out[t] = s;
+    return;
+  }
   const int64_t lim = s + 65536;  // Block.MAX_BLOCK_SIZE probes
   int64_t best = -1;
   const int64_t qe = max(s, D - 17);  // q + 18 > D: EOF while reading the first header → accepted
