@@ -474,6 +474,15 @@ int sbam_write_bai(sbam_ctx *ctx, uint8_t *out, int64_t cap, int64_t *n_bytes);
  * no reference counterpart, Index.scala:53-90 only reads): for tests that must reach that path. */
 int sbam_index_long_cigar_ops(void);
 
+/* ---- for tests: the library's prefix-sum primitives (no reference counterpart; no context: each call allocates its
+ * device buffers, runs on a stream of its own, copies back and frees) ------------------------------------------- */
+/* The in-place exclusive scan behind every offsets column (SAM spec §4.2's variable-length fields as CSR offsets):
+ * in holds cols columns of n values; out receives cols columns of n + 1: the exclusive prefix sums and the total. */
+int sbam_test_exclusive_scan(int device, const int64_t *in, int64_t n, int32_t cols, int64_t *out);
+/* One workgroup's scan of n per-workgroup sums (the step between the passes of a device-wide scan; BGZF chunk counts,
+ * MetadataStream.scala:23-54): out receives n exclusive prefix sums as int64 and, at [n], the total. */
+int sbam_test_scan_sums_int(int device, const int32_t *in, int64_t n, int64_t *out);
+
 /* ---- timing support for bench/profiling -------------------------------------------------------- */
 /* Device time (ms, HIP events on the library's stream) of the most recent launch of a named kernel
  * family: "scan", "inflate", "check_full", "check_eager", "records", "load_records", "record_fields" (the gather of

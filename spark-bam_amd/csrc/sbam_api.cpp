@@ -438,7 +438,7 @@ TagLayout tag_layout(size_t n, size_t nq, size_t nb) {
   t.ostride = up256((n + 1) * 8);
   t.src = nb * t.ostride;
   t.bsum = t.src + nb * up256(n * 8);
-  t.small = t.bsum + up256(nb * (size_t)tag_scan_blocks((int64_t)n) * 8);
+  t.small = t.bsum + up256(nb * (size_t)exclusive_scan_blocks((int64_t)n) * 8);
   t.off_bytes = t.small + up256(kTagSmallWords * 8);
   return t;
 }
@@ -671,7 +671,7 @@ static int scan_candidates(sbam_ctx *c) {
   HIPCHK(c, ensure_scan(c, c->D));
   // one pass into per-chunk slots (+ counts, exact even past the slots); d_small[0] = total, [1] = overflow
   HIPCHK(c, launch_scan_slots(c->d_comp, c->D, c->d_cc, nchunks, c->d_slots, c->d_small + 1, c->stream));
-  HIPCHK(c, launch_scan_prefix(c->d_cc, nchunks, c->d_coff, c->d_small, c->stream));
+  HIPCHK(c, launch_scan_sums(c->d_cc, c->d_coff, nchunks, 1, c->d_small, c->stream));
   int64_t tot_ovf[2] = {0, 0};
   HIPCHK(c, hipMemcpyAsync(tot_ovf, c->d_small, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1700,8 +1700,8 @@ int sbam_load_record_tags(sbam_ctx *c, int64_t i0, int64_t n, const sbam_tag_que
     HIPCHK(c, hipMemsetAsync(small, 0, kTagSmallWords * 8, c->stream));
     HIPCHK(c, hipMemsetAsync(small, 0xff, 8, c->stream));
     HIPCHK(c, launch_tag_walk(wa, c->stream));
-    HIPCHK(c, launch_tag_scan(wa.off, wa.ostride, n, nb, reinterpret_cast<int64_t *>(ob + lay.bsum),
-                              small + 1, c->stream));
+    HIPCHK(c, launch_exclusive_scan(wa.off, wa.ostride, n, nb, reinterpret_cast<int64_t *>(ob + lay.bsum),
+                                    small + 1, c->stream));
   }
   std::vector<int64_t> h(kTagSmallWords);
   HIPCHK(c, hipMemcpyAsync(h.data(), small, kTagSmallWords * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1990,6 +1990,58 @@ int sbam_write_bai(sbam_ctx *c, uint8_t *out, int64_t cap, int64_t *n_bytes) {
                                    t.n_no_coor, out, cap, n_bytes);
   if (rc) return set_err(c, rc, "sbam_write_bai: %lld bytes needed, capacity %lld", (long long)*n_bytes, (long long)cap);
   return SBAM_OK;
+}
+
+// ---- test support: the scan launchers on buffers and a stream of their own (no context) -------------------------
+namespace {
+struct ScanTest {  // a device, a stream and one allocation, released on every path
+  hipStream_t stream = nullptr;
+  uint8_t *buf = nullptr;
+  hipError_t open(int device, size_t bytes) {
+    HIPTRY(hipSetDevice(device));
+    HIPTRY(hipStreamCreate(&stream));
+    return hipMalloc(reinterpret_cast<void **>(&buf), bytes ? bytes : 8);
+  }
+  ~ScanTest() {
+    if (buf) (void)hipFree(buf);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+}  // namespace
+
+int sbam_test_exclusive_scan(int device, const int64_t *in, int64_t n, int32_t cols, int64_t *out) {
+  if (n < 0 || cols < 1 || !out || (n && !in)) return SBAM_ERR_ARG;
+  const size_t N = (size_t)n, C = (size_t)cols, stride = N + 1, nblk = (size_t)exclusive_scan_blocks(n);
+  ScanTest t;
+  if (t.open(device, (C * stride + C * nblk + C) * 8) != hipSuccess) return SBAM_ERR_HIP;
+  int64_t *off = reinterpret_cast<int64_t *>(t.buf), *bsum = off + C * stride, *totals = bsum + C * nblk;
+  std::vector<int64_t> tot(C);
+  hipError_t e = hipMemsetAsync(t.buf, 0xff, (C * stride + C * nblk + C) * 8, t.stream);
+  if (e == hipSuccess && n)
+    e = hipMemcpy2DAsync(off, stride * 8, in, N * 8, N * 8, C, hipMemcpyHostToDevice, t.stream);
+  if (e == hipSuccess) e = launch_exclusive_scan(off, (int64_t)stride, n, cols, bsum, totals, t.stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out, off, C * stride * 8, hipMemcpyDeviceToHost, t.stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(tot.data(), totals, C * 8, hipMemcpyDeviceToHost, t.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(t.stream);
+  if (e != hipSuccess) return SBAM_ERR_HIP;
+  for (size_t c = 0; c < C; c++)  // the totals pointer and the column's last entry are one number
+    if (tot[c] != out[c * stride + N]) return SBAM_ERR_STATE;
+  return SBAM_OK;
+}
+
+int sbam_test_scan_sums_int(int device, const int32_t *in, int64_t n, int64_t *out) {
+  if (n < 0 || !out || (n && !in)) return SBAM_ERR_ARG;
+  const size_t N = (size_t)n, in_bytes = (N * 4 + 7) & ~(size_t)7;
+  ScanTest t;
+  if (t.open(device, in_bytes + (N + 1) * 8) != hipSuccess) return SBAM_ERR_HIP;
+  const int32_t *d_in = reinterpret_cast<const int32_t *>(t.buf);
+  int64_t *d_out = reinterpret_cast<int64_t *>(t.buf + in_bytes);
+  hipError_t e = hipMemsetAsync(d_out, 0xff, (N + 1) * 8, t.stream);
+  if (e == hipSuccess && n) e = hipMemcpyAsync(t.buf, in, N * 4, hipMemcpyHostToDevice, t.stream);
+  if (e == hipSuccess) e = launch_scan_sums(d_in, d_out, n, 1, d_out + n, t.stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (N + 1) * 8, hipMemcpyDeviceToHost, t.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(t.stream);
+  return e == hipSuccess ? SBAM_OK : SBAM_ERR_HIP;
 }
 
 }  // extern "C"

@@ -6,21 +6,11 @@
 //  The record-boundary checker and record chain live in sbam_check.hip.
 //
 // All byte/integer work: no MFMA (no dense contraction).  Design notes and rooflines: DESIGN.md.
+#include "sbam_device.h"
 #include "sbam_internal.h"
 
 namespace sbam {
 
-#define SB_DEV __device__ __forceinline__
-
-// ------------------------------------------------------------------------------------------------
-// wave helpers (wave64)
-// ------------------------------------------------------------------------------------------------
-SB_DEV int lane_id() { return __lane_id(); }
-SB_DEV uint32_t wave_or(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v |= __shfl_xor(v, o, 64);
-  return v;
-}
 SB_DEV uint32_t brev(uint32_t code, int len) { return __builtin_bitreverse32(code) >> (32 - len); }
 
 // ================================================================================================
@@ -74,32 +64,6 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_count(const uint8_t *__re
   if (threadIdx.x == 0) chunk_counts[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
 }
 
-// Exclusive prefix over chunk counts: one workgroup (chunk count is D / 1 MiB: ~10^4 for 10 GB).
-__global__ __launch_bounds__(1024) void k_scan_prefix(const int32_t *__restrict__ cnt, int64_t n,
-                                                       int64_t *__restrict__ off, int64_t *__restrict__ total) {
-  __shared__ int64_t s[1024];
-  __shared__ int64_t carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int64_t b = 0; b < n; b += 1024) {
-    const int64_t i = b + threadIdx.x;
-    const int64_t v = i < n ? cnt[i] : 0;
-    s[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-      const int64_t t = threadIdx.x >= o ? s[threadIdx.x - o] : 0;
-      __syncthreads();
-      s[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < n) off[i] = carry + s[threadIdx.x] - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry += s[1023];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = carry;
-}
-
 SB_DEV void fill_candidate(const uint8_t *d, int64_t D, int64_t q, Candidate &c) {
   const int32_t xlen = (int32_t)d[q + 10] | ((int32_t)d[q + 11] << 8);
   const int32_t hs = 18 + xlen - 6;
@@ -143,11 +107,7 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_write(const uint8_t *__re
     __syncthreads();
     if (s_any) {  // rare: ordered rank = wave prefix + preceding waves
       const int c = __popc(bits);
-      int incl = c;
-      for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o, 64);
-        if (lane_id() >= o) incl += t;
-      }
+      const int incl = wave_incl_scan(c);
       if (lane_id() == 63) s_wsum[threadIdx.x >> 6] = incl;
       __syncthreads();
       int before = incl - c;
@@ -224,11 +184,7 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_slots_wide(const uint8_t 
     ph = nx;
     if (any) {  // rare: ordered rank = wave prefix + preceding waves
       const int c = __popcll(bits);
-      int incl = c;
-      for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o, 64);
-        if (lane_id() >= o) incl += t;
-      }
+      const int incl = wave_incl_scan(c);
       if (lane_id() == 63) s_wsum[threadIdx.x >> 6] = incl;
       __syncthreads();
       int slot = run + incl - c;
@@ -323,11 +279,6 @@ __global__ void k_lower_bound(const Candidate *__restrict__ c, int64_t n, int64_
   *out = cand_lower_bound(c, 0, n, q);
 }
 
-SB_DEV int64_t wave_sum64(int64_t v) {
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // The block table's columns from the verified chain, plus each workgroup's sum of uncompressed sizes for
 // k_block_uoff (a negative isize counts 0, as MetadataStream's offsets do).
 __global__ __launch_bounds__(256) void k_gather_blocks(const Candidate *__restrict__ c, int64_t first, int64_t n,
@@ -345,7 +296,7 @@ __global__ __launch_bounds__(256) void k_gather_blocks(const Candidate *__restri
     us[i] = ci.isize;
     u = ci.isize < 0 ? 0 : ci.isize;
   }
-  u = wave_sum64(u);
+  u = wave_sum(u);
   if (lane_id() == 0) s[threadIdx.x >> 6] = u;
   __syncthreads();
   if (threadIdx.x == 0) wsum[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
@@ -355,23 +306,17 @@ __global__ __launch_bounds__(256) void k_gather_blocks(const Candidate *__restri
 // up the sums of the workgroups before it (n / 256 of them at most, from L2), then scans its own 256 blocks.
 __global__ __launch_bounds__(256) void k_block_uoff(const int32_t *__restrict__ us, int64_t n,
                                                     const int64_t *__restrict__ wsum, int64_t *__restrict__ uoff) {
-  __shared__ int64_t s[8];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  __shared__ int64_t s[4], ws[4];
+  const int t = threadIdx.x;
   int64_t b = 0;
   for (int64_t k = t; k < (int64_t)blockIdx.x; k += 256) b += wsum[k];
-  b = wave_sum64(b);
-  if (lane == 0) s[w] = b;
+  b = wave_sum(b);
+  if (lane_id() == 0) s[t >> 6] = b;
   const int64_t i = (int64_t)blockIdx.x * 256 + t;
   const int64_t v = i < n ? (us[i] < 0 ? 0 : us[i]) : 0;
-  int64_t x = v;  // inclusive scan within the wave
-  for (int o = 1; o < 64; o <<= 1) {
-    const int64_t y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) s[4 + w] = x;
-  __syncthreads();
-  int64_t base = s[0] + s[1] + s[2] + s[3];
-  for (int k = 0; k < w; k++) base += s[4 + k];
+  int64_t total;
+  const int64_t x = block_incl_scan<int64_t, 256>(v, total, ws);  // (its barriers publish s too)
+  const int64_t base = s[0] + s[1] + s[2] + s[3];
   if (i < n) uoff[i] = base + x - v;
   if (i == n - 1) uoff[n] = base + x;
 }
@@ -383,10 +328,6 @@ __global__ __launch_bounds__(256) void k_block_uoff(const int32_t *__restrict__ 
 hipError_t launch_scan_count(const uint8_t *d, int64_t D, int32_t *cc, int64_t nchunks, hipStream_t s) {
   if (nchunks == 0) return hipSuccess;
   hipLaunchKernelGGL(k_scan_count, dim3((unsigned)nchunks), dim3(kScanThreads), 0, s, d, D, cc);
-  return hipGetLastError();
-}
-hipError_t launch_scan_prefix(int32_t *cc, int64_t nchunks, int64_t *off, int64_t *total, hipStream_t s) {
-  hipLaunchKernelGGL(k_scan_prefix, dim3(1), dim3(1024), 0, s, cc, nchunks, off, total);
   return hipGetLastError();
 }
 hipError_t launch_scan_write(const uint8_t *d, int64_t D, const int64_t *off, int64_t nchunks, Candidate *c,

@@ -21,11 +21,10 @@
 #include <atomic>
 #include <type_traits>
 
+#include "sbam_device.h"
 #include "sbam_internal.h"
 
 namespace sbam {
-
-#define SB_DEV __device__ __forceinline__
 
 constexpr uint32_t W_SUCC = 0x80000000u, W_HALO = 0x00800000u;
 constexpr uint32_t W_PASS0 = 0x40000000u;  // internal: first record passed, chain pending
@@ -45,30 +44,9 @@ constexpr int kFlushTiles = 7;              // 7 tiles x 32 positions per lane <
 static_assert(kWin % 16 == 0, "window");
 static_assert((kTile / (4 * kCheckThreads)) % 2 == 0, "groups pair up within a tile (add4_paired)");
 
-SB_DEV int lane_id() { return __lane_id(); }
-
 SB_DEV uint64_t shfl_xor64(uint64_t v, int m) {
   const uint32_t lo = __shfl_xor((int)(uint32_t)v, m, 64), hi = __shfl_xor((int)(uint32_t)(v >> 32), m, 64);
   return ((uint64_t)hi << 32) | lo;
-}
-SB_DEV uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor((int)v, o, 64);
-  return v;
-}
-SB_DEV uint32_t wave_incl_scan_u32(uint32_t v) {
-  const int lane = __lane_id();
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = (uint32_t)__shfl_up((int)v, d, 64);
-    if (lane >= d) v += y;
-  }
-  return v;
-}
-SB_DEV uint32_t wave_or(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v |= __shfl_xor((int)v, o, 64);
-  return v;
 }
 
 // ---- byte-class SWAR ---------------------------------------------------------------------------
@@ -273,7 +251,7 @@ __global__ __launch_bounds__(256) void k_chains(StreamView sv, int64_t x0, int64
   const int64_t x0a = x0 & ~(int64_t)63;
   const int64_t nwords = (x1 - x0a + 63) >> 6;
   const int64_t nchunks = (nwords + kChainWords - 1) / kChainWords;
-  const int tid = threadIdx.x, lane = lane_id(), wv = tid >> 6;
+  const int tid = threadIdx.x, lane = lane_id();
   uint32_t n_succ = 0;
   for (int64_t ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
     const int64_t w0 = ch * kChainWords + (int64_t)tid * kChainWordsPerThread;
@@ -284,23 +262,10 @@ __global__ __launch_bounds__(256) void k_chains(StreamView sv, int64_t x0, int64
       cw[j] = w0 + j < nwords ? bitmap[w0 + j] : 0ull;
       mine += (uint32_t)__popcll(cw[j]);
     }
-    // workgroup exclusive scan of the per-thread counts
-    uint32_t incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    __syncthreads();  // s_wsum / s_list of the previous chunk are no longer read
-    if (lane == 63) s_wsum[wv] = incl;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      before += k < wv ? s_wsum[k] : 0u;
-      total += s_wsum[k];
-    }
-    const uint32_t first = before + incl - mine;
+    // workgroup exclusive scan of the per-thread counts (s_list of the previous chunk is no longer read: the barrier
+    // behind its last round)
+    uint32_t total;
+    const uint32_t first = block_incl_scan<uint32_t, 256>(mine, total, s_wsum) - mine;
     const int64_t cbase = x0a + ch * (int64_t)kChainWords * 64;
     for (uint32_t r0 = 0; r0 < total; r0 += kChainList) {
       if (mine && first < r0 + kChainList && first + mine > r0) {
@@ -368,36 +333,6 @@ __global__ __launch_bounds__(256) void k_p0_count_tiles(const int32_t *__restric
   chunk_cnt[ch] = c;
 }
 
-// exclusive scan of the chunk counts (one workgroup): off[ch], and off[n] = total.  Thread t owns the contiguous run
-// [t·per, (t + 1)·per) of the counts: it sums its run, one workgroup scan of the 1024 sums gives every run its
-// base, and the run is written out (two passes over n integers instead of n / 1024 barrier-separated rounds:
-// 311 -> ~20 us for the 206 K chunks of a 10 GB shard).
-__global__ __launch_bounds__(1024) void k_p0_scan(const int32_t *__restrict__ cnt, int64_t n, int64_t *__restrict__ off) {
-  __shared__ int64_t s_w[16];
-  const int lane = lane_id(), wv = threadIdx.x >> 6;
-  const int64_t per = (n + 1023) / 1024;
-  const int64_t b = min((int64_t)threadIdx.x * per, n), e = min(b + per, n);
-  int64_t sum = 0;
-#pragma unroll 8
-  for (int64_t i = b; i < e; i++) sum += cnt[i];
-  int64_t incl = sum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int64_t t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) s_w[wv] = incl;
-  __syncthreads();
-  int64_t run = incl - sum;
-  for (int k = 0; k < wv; k++) run += s_w[k];
-#pragma unroll 8
-  for (int64_t i = b; i < e; i++) {
-    off[i] = run;
-    run += cnt[i];
-  }
-  if (threadIdx.x == 1023) off[n] = run;  // (thread 1023's run ends at n: b and e are clamped to n)
-}
-
 __global__ __launch_bounds__(256) void k_p0_list(const unsigned long long *__restrict__ bitmap, int64_t nwords,
                                                  int64_t x0a, const int64_t *__restrict__ chunk_off,
                                                  int64_t *__restrict__ list) {
@@ -423,19 +358,9 @@ __global__ __launch_bounds__(256) void k_p0_list(const unsigned long long *__res
     cw[j] = s_cw[threadIdx.x * kRow + j];
     mine += (uint32_t)__popcll(cw[j]);
   }
-  const int lane = lane_id(), wv = threadIdx.x >> 6;
-  uint32_t incl = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
   __shared__ uint32_t s_w[4];
-  if (lane == 63) s_w[wv] = incl;
-  __syncthreads();
-  uint32_t before = 0;
-  for (int k = 0; k < wv; k++) before += s_w[k];
-  int64_t idx = chunk_off[blockIdx.x] + before + incl - mine;
+  uint32_t total;
+  int64_t idx = chunk_off[blockIdx.x] + block_incl_scan<uint32_t, 256>(mine, total, s_w) - mine;
 #pragma unroll
   for (int j = 0; j < kChainWordsPerThread; j++)
     for (unsigned long long m = cw[j]; m; m &= m - 1) list[idx++] = x0a + ((w0 + j) << 6) + __builtin_ctzll(m);
@@ -1829,7 +1754,7 @@ __global__ __launch_bounds__(64 * kEwWaves) void k_eager_wave(StreamView sv, int
       cnt += (uint32_t)__popc(S[k]);
       reinterpret_cast<uint16_t *>(bm)[64 * k + lane] = (uint16_t)S[k];
     }
-    const uint32_t incl = wave_incl_scan_u32(cnt), total = (uint32_t)__shfl((int)incl, 63, 64);
+    const uint32_t incl = wave_incl_scan(cnt), total = (uint32_t)__shfl((int)incl, 63, 64);
     for (uint32_t r0 = 0; r0 < total; r0 += kEwQ) {  // (one round unless the tile has > kEwQ survivors)
       uint32_t at = incl - cnt;
       if (at < r0 + kEwQ && at + cnt > r0) {
@@ -2074,8 +1999,8 @@ hipError_t launch_chain_list_build(int64_t x0, int64_t x1, const unsigned long l
                        ntiles_of(x0, x1), nch, cs.chunk_cnt);
   else
     hipLaunchKernelGGL(k_p0_count, dim3((unsigned)nch), dim3(256), 0, s, bitmap, nwords, cs.chunk_cnt);
-  hipLaunchKernelGGL(k_p0_scan, dim3(1), dim3(1024), 0, s, cs.chunk_cnt, nch, cs.chunk_off);
-  return hipGetLastError();
+  // exclusive offsets of the chunk counts; chunk_off[nch] = the number of PASS0 positions
+  return launch_scan_sums(cs.chunk_cnt, cs.chunk_off, nch, 1, cs.chunk_off + nch, s);
 }
 hipError_t launch_chain_list_run(StreamView sv, int64_t x0, int64_t x1, int32_t R, int32_t by_key, CountsDev cd,
                                  unsigned long long *bitmap, const ChainScratch &cs, hipStream_t s) {

@@ -8,7 +8,7 @@
 //   sizes    one thread per record reads the fixed-field columns (coalesced; the stream is not touched), computes
 //            the four lengths and validates them against block_size and the stream end; the first bad record index
 //            is reduced to the host, which then launches no gather.
-//   scan     per-workgroup sums, one workgroup over the sums, per-workgroup offsets (int64).
+//   scan     per-workgroup sums, launch_scan_sums over the four columns of sums, per-workgroup offsets (int64).
 //   gather   work is divided over OUTPUT bytes: a workgroup owns an 8 KiB tile of one column; the records that
 //            intersect it come from a binary search in the offsets (one thread per tile, ahead of the gather),
 //            their offsets and field positions are staged in LDS when they fit, and every lane builds 8 output
@@ -20,11 +20,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sbam_device.h"
 #include "sbam_internal.h"
 
 namespace sbam {
-
-#define SB_DEV __device__ __forceinline__
 
 int64_t field_gather_tiles(int64_t total);
 
@@ -39,34 +38,6 @@ constexpr int kStepBytes = kGatherThreads * kLaneBytes;  // 2 KiB of one output 
 constexpr int field_steps(int field) { return field == 1 ? 2 : 4; }
 constexpr int kStageCap = 1040;      // a tile's records kept in LDS (more: searched in global memory)
 
-// inclusive scan of four int64 per thread across the workgroup; total[f] = the workgroup's sum
-SB_DEV void block_scan4(const int64_t v[4], int64_t incl[4], int64_t total[4], int64_t (*ws)[4]) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-  for (int f = 0; f < 4; f++) {
-    long long s = v[f];
-    for (int o = 1; o < 64; o <<= 1) {
-      const long long t = __shfl_up(s, o);
-      if (lane >= o) s += t;
-    }
-    incl[f] = s;
-    if (lane == 63) ws[w][f] = s;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int f = 0; f < 4; f++) {
-    int64_t before = 0, tot = 0;
-    for (int k = 0; k < nw; k++) {
-      const int64_t x = ws[k][f];
-      if (k < w) before += x;
-      tot += x;
-    }
-    incl[f] += before;
-    total[f] = tot;
-  }
-  __syncthreads();
-}
-
 // bsum[f * nblk + b] = workgroup b's sum of length f; *first_bad = min index of a record that fails validation
 __global__ void __launch_bounds__(kSizeThreads) k_field_sums(FieldSizesArgs a, int64_t nblk, int64_t *__restrict__ bsum,
                                                              unsigned long long *__restrict__ first_bad) {
@@ -76,29 +47,8 @@ __global__ void __launch_bounds__(kSizeThreads) k_field_sums(FieldSizesArgs a, i
   if (k < a.n) r = field_lens(a, k);
   if (r.bad) atomicMin(first_bad, (unsigned long long)k);
   int64_t incl[4], total[4];
-  block_scan4(r.v, incl, total, ws);
+  block_incl_scan<int64_t, 4, kSizeThreads>(r.v, incl, total, ws);
   if (threadIdx.x < 4) bsum[threadIdx.x * nblk + blockIdx.x] = total[threadIdx.x];
-}
-
-// one workgroup: bsum[f][*] -> exclusive prefix sums in place, totals[f] = the column's length
-__global__ void __launch_bounds__(kSizeThreads) k_field_scan_sums(int64_t nblk, int64_t *__restrict__ bsum,
-                                                                  int64_t *__restrict__ totals) {
-  __shared__ int64_t ws[kSizeThreads / 64][4];
-  int64_t run[4] = {0, 0, 0, 0};
-  for (int64_t b0 = 0; b0 < nblk; b0 += kSizeThreads) {
-    const int64_t b = b0 + threadIdx.x;
-    int64_t v[4], incl[4], total[4];
-#pragma unroll
-    for (int f = 0; f < 4; f++) v[f] = b < nblk ? bsum[f * nblk + b] : 0;
-    block_scan4(v, incl, total, ws);
-#pragma unroll
-    for (int f = 0; f < 4; f++) {
-      if (b < nblk) bsum[f * nblk + b] = run[f] + incl[f] - v[f];
-      run[f] += total[f];
-    }
-  }
-  if (threadIdx.x == 0)
-    for (int f = 0; f < 4; f++) totals[f] = run[f];
 }
 
 // off[f][k] = exclusive prefix sum of length f over the batch's records, off[f][n] = its total
@@ -109,7 +59,7 @@ __global__ void __launch_bounds__(kSizeThreads) k_field_offsets(FieldSizesArgs a
   FieldLens r{{0, 0, 0, 0}, false};
   if (k < a.n) r = field_lens(a, k);
   int64_t incl[4], total[4];
-  block_scan4(r.v, incl, total, ws);
+  block_incl_scan<int64_t, 4, kSizeThreads>(r.v, incl, total, ws);
   if (k >= a.n) return;
   int64_t *o[4] = {off.name, off.cigar, off.seq, off.aux};
 #pragma unroll
@@ -270,7 +220,8 @@ hipError_t launch_field_sizes(const FieldSizesArgs &a, int64_t *bsum, FieldOffse
   hipError_t e = hipMemsetAsync(first_bad, 0xff, sizeof(unsigned long long), s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_field_sums, dim3((unsigned)nblk), dim3(kSizeThreads), 0, s, a, nblk, bsum, first_bad);
-  hipLaunchKernelGGL(k_field_scan_sums, dim3(1), dim3(kSizeThreads), 0, s, nblk, bsum, totals);
+  e = launch_scan_sums(bsum, bsum, nblk, 4, totals, s);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_field_offsets, dim3((unsigned)nblk), dim3(kSizeThreads), 0, s, a, nblk, bsum, off);
   return hipGetLastError();
 }

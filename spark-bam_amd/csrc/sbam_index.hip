@@ -12,7 +12,7 @@
 //   stats    one lane per record: run head (the (ref_id, bin) of record i - 1 differs), order violation, and the
 //            per-reference counters, reduced inside the wave before any global atomic (a coordinate-sorted file has
 //            one reference per wave almost everywhere); per-workgroup head counts for the compaction.
-//   scan     one workgroup: exclusive sums of the head counts, their total = n_runs.
+//   scan     launch_scan_sums: exclusive sums of the head counts, their total = n_runs.
 //   runs     scan of the head flags inside the workgroup; a head scatters (ref, bin, vbeg), a tail its vend.
 //   linear   one lane per record: atomicMin(vbeg) into every 16 kb window the record touches that record i - 1 does
 //            not touch on the same reference (the predecessor's vbeg is smaller, so skipping is exact for any order
@@ -24,11 +24,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sbam_device.h"
 #include "sbam_internal.h"
 
 namespace sbam {
-
-#define SB_DEV __device__ __forceinline__
 
 namespace {
 
@@ -86,46 +85,6 @@ SB_DEV int64_t beg_of(const IndexArgs &a, int64_t i) {
 }
 
 SB_DEV bool placed(const IndexArgs &a, int64_t i) { return (uint32_t)a.ref_id[i] < (uint32_t)a.nref; }
-
-template <class T>
-SB_DEV T wave_sum(T v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-SB_DEV u64 wave_min(u64 v) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const u64 t = __shfl_xor(v, o);
-    v = t < v ? t : v;
-  }
-  return v;
-}
-SB_DEV u64 wave_max(u64 v) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const u64 t = __shfl_xor(v, o);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-
-// inclusive scan of one int per thread across the workgroup; *total = the workgroup's sum
-SB_DEV int block_scan(int v, int *total, int *ws) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  int s = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(s, o);
-    if (lane >= o) s += t;
-  }
-  if (lane == 63) ws[w] = s;
-  __syncthreads();
-  int before = 0, tot = 0;
-  for (int k = 0; k < nw; k++) {
-    const int x = ws[k];
-    if (k < w) before += x;
-    tot += x;
-  }
-  *total = tot;
-  return s + before;
-}
 
 // spans: end_out[i], bin_out[i] of every record; a[0] of the stats words = first offending stream offset
 __global__ void __launch_bounds__(kIndexThreads) k_index_spans(IndexArgs a, IndexStats st) {
@@ -224,36 +183,8 @@ __global__ void __launch_bounds__(kIndexThreads) k_index_stats(IndexArgs a, Inde
     atomicMax(st.n_intv + ref, nintv);
   }
   int total;
-  (void)block_scan(head, &total, ws);
+  (void)block_incl_scan<int, kIndexThreads>(head, total, ws);
   if (threadIdx.x == 0) heads[blockIdx.x] = total;
-}
-
-// one workgroup: heads[*] -> exclusive prefix sums in place; the stats word 3 = their total (n_runs)
-__global__ void __launch_bounds__(kIndexThreads) k_index_scan(int64_t nblk, int64_t *__restrict__ heads, IndexStats st) {
-  __shared__ int64_t ws[kIndexThreads / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int64_t run = 0;
-  for (int64_t b0 = 0; b0 < nblk; b0 += kIndexThreads) {
-    const int64_t b = b0 + threadIdx.x;
-    const int64_t v = b < nblk ? heads[b] : 0;
-    long long s = v;
-    for (int o = 1; o < 64; o <<= 1) {
-      const long long t = __shfl_up(s, o);
-      if (lane >= o) s += t;
-    }
-    if (lane == 63) ws[w] = s;
-    __syncthreads();
-    int64_t before = 0, tot = 0;
-    for (int k = 0; k < kIndexThreads / 64; k++) {
-      const int64_t x = ws[k];
-      if (k < w) before += x;
-      tot += x;
-    }
-    if (b < nblk) heads[b] = run + before + s - v;
-    run += tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) st.w[3] = (u64)run;
 }
 
 // runs: run k = (ref, bin, vbeg of its head, vend of its tail); heads[] holds the exclusive sums
@@ -270,7 +201,7 @@ __global__ void __launch_bounds__(kIndexThreads) k_index_runs(IndexArgs a, const
     tail = i + 1 == a.n || a.ref_id[i + 1] != ref || a.bin_out[i + 1] != bin;
   }
   int total;
-  const int incl = block_scan(head, &total, ws);
+  const int incl = block_incl_scan<int, kIndexThreads>(head, total, ws);
   if (!on_ref) return;
   const int64_t k = heads[blockIdx.x] + incl - 1;  // the run this record belongs to
   if (k < 0 || k >= r.n) return;
@@ -334,8 +265,7 @@ hipError_t launch_index_pass1(const IndexArgs &a, IndexStats st, int64_t *heads,
   const int64_t nblk = index_blocks(a.n);
   hipLaunchKernelGGL(k_index_spans, dim3((unsigned)nblk), dim3(kIndexThreads), 0, s, a, st);
   hipLaunchKernelGGL(k_index_stats, dim3((unsigned)nblk), dim3(kIndexThreads), 0, s, a, st, heads);
-  hipLaunchKernelGGL(k_index_scan, dim3(1), dim3(kIndexThreads), 0, s, nblk, heads, st);
-  return hipGetLastError();
+  return launch_scan_sums(heads, heads, nblk, 1, reinterpret_cast<int64_t *>(st.w + 3), s);
 }
 
 hipError_t launch_index_pass2(const IndexArgs &a, const int64_t *heads, IndexRuns r, const int64_t *intv_off,

@@ -79,8 +79,6 @@ hipError_t launch_scan_slots(const uint8_t *d, int64_t D, int32_t *chunk_counts,
                              int64_t *overflow, hipStream_t s);
 hipError_t launch_scan_compact(const Candidate *slots, const int32_t *chunk_counts, const int64_t *chunk_offsets,
                                int64_t nchunks, Candidate *out, hipStream_t s);
-hipError_t launch_scan_prefix(int32_t *chunk_counts, int64_t nchunks, int64_t *chunk_offsets, int64_t *total,
-                              hipStream_t s);
 hipError_t launch_scan_write(const uint8_t *d, int64_t D, const int64_t *chunk_offsets, int64_t nchunks,
                              Candidate *cands, hipStream_t s);
 hipError_t launch_chain_verify(const Candidate *cands, int64_t ncand, int64_t first, int64_t D, int64_t *first_stop,
@@ -280,10 +278,16 @@ struct TagWalkArgs {
 };
 constexpr int kTagPresentSlots = 64;
 int tag_long_aux_bytes();
-int64_t tag_scan_blocks(int64_t n);  // entries per byte column of launch_tag_scan's bsum scratch
 hipError_t launch_tag_walk(const TagWalkArgs &a, hipStream_t s);
-// off[b * ostride + k], k < n: lengths -> exclusive prefix sums, [n] = totals[b] = the column's bytes
-hipError_t launch_tag_scan(int64_t *off, int64_t ostride, int64_t n, int32_t nb, int64_t *bsum, int64_t *totals,
-                           hipStream_t s);
+
+// Prefix sums (sbam_scan.hip).  Column c of `cols`: out[c * n + i] = the sum of in[c * n + j] over j < i, as int64,
+// and totals[c] = the column's sum; one workgroup per column.  out may be in (int64).
+hipError_t launch_scan_sums(const int32_t *in, int64_t *out, int64_t n, int32_t cols, int64_t *totals, hipStream_t s);
+hipError_t launch_scan_sums(const int64_t *in, int64_t *out, int64_t n, int32_t cols, int64_t *totals, hipStream_t s);
+// off[c * stride + k], k < n: values -> exclusive prefix sums in place, [n] = totals[c] = the column's sum.
+// bsum: cols * exclusive_scan_blocks(n) int64 of scratch.
+int64_t exclusive_scan_blocks(int64_t n);
+hipError_t launch_exclusive_scan(int64_t *off, int64_t stride, int64_t n, int32_t cols, int64_t *bsum, int64_t *totals,
+                                 hipStream_t s);
 
 }  // namespace sbam

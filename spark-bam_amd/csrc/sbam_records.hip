@@ -20,11 +20,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sbam_device.h"
 #include "sbam_internal.h"
 
 namespace sbam {
-
-#define SB_DEV __device__ __forceinline__
 
 namespace {
 
@@ -216,11 +215,7 @@ __global__ void __launch_bounds__(256) k_split_offsets(const unsigned long long 
     }
     const uint32_t pc = (uint32_t)__popcll(m);
     // inclusive scan across the wave, then across the 4 waves
-    uint32_t s = pc;
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t t = __shfl_up(s, o);
-      if (lane >= o) s += t;
-    }
+    const uint32_t s = wave_incl_scan(pc);
     if (lane == 63) wsum[wv] = s;
     __syncthreads();
     uint32_t before = 0, total = 0;

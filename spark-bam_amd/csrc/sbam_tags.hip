@@ -17,8 +17,8 @@
 //   long     a record with more than kLongAuxBytes tag bytes is not staged: after the rounds the workgroup's waves
 //            take its long records in turn and walk them in global memory, lane 0 reading each header (8 bytes,
 //            broadcast) and all 64 lanes searching a Z or H value's NUL 256 bytes a step with a ballot.
-//   scan     the byte columns' lengths become exclusive int64 prefix sums in place (per-workgroup sums, one
-//            workgroup over the sums, per-workgroup offsets), one grid row per column.
+//   scan     the byte columns' lengths become exclusive int64 prefix sums in place (launch_exclusive_scan,
+//            sbam_scan.hip), one grid row per column.
 //   bytes    sbam_fields.hip's gather (work divided over output bytes) with each record's source position taken from
 //            the column the walk wrote: record offset + tag start + rel.
 //
@@ -30,35 +30,24 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sbam_device.h"
 #include "sbam_internal.h"
 #include "sbam_tag_core.h"
 
 namespace sbam {
-
-#define SB_DEV __device__ __forceinline__
 
 namespace {
 
 constexpr int kWalkThreads = 256;  // records per workgroup
 constexpr int kWalkWaves = kWalkThreads / 64;
 constexpr int kStageBytes = 30720;
-constexpr int kScanThreads = 1024;
 static_assert(sbam_tag::kLongAuxBytes + 8 <= kStageBytes, "one short record must fit the stage");
 static_assert(sbam_tag::kLongAuxBytes < 65536, "found positions are uint16");
 
 // exclusive prefix sums of one int32 per thread over the workgroup into pre[0 .. kWalkThreads]
 SB_DEV void walk_scan(int32_t v, int32_t *pre, int32_t *ws) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int32_t s = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int32_t t = __shfl_up(s, o);
-    if (lane >= o) s += t;
-  }
-  if (lane == 63) ws[w] = s;
-  __syncthreads();
-  int32_t before = 0;
-  for (int k = 0; k < w; k++) before += ws[k];
-  pre[threadIdx.x + 1] = before + s;
+  int32_t total;
+  pre[threadIdx.x + 1] = block_incl_scan<int32_t, kWalkThreads>(v, total, ws);
   if (threadIdx.x == 0) pre[0] = 0;
   __syncthreads();
 }
@@ -229,90 +218,15 @@ __global__ void __launch_bounds__(kWalkThreads) k_tag_walk(TagWalkArgs a) {
     atomicAdd(&a.present[(blockIdx.x % kTagPresentSlots) * sbam_tag::kMaxTags + tid], (unsigned long long)spresent[tid]);
 }
 
-// inclusive scan of one int64 per thread across the workgroup; *total = the workgroup's sum
-SB_DEV int64_t block_scan1(int64_t v, int64_t *total, int64_t *ws) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  long long s = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const long long t = __shfl_up(s, o);
-    if (lane >= o) s += t;
-  }
-  if (lane == 63) ws[w] = s;
-  __syncthreads();
-  int64_t before = 0, tot = 0;
-  for (int k = 0; k < nw; k++) {
-    const int64_t y = ws[k];
-    if (k < w) before += y;
-    tot += y;
-  }
-  __syncthreads();
-  *total = tot;
-  return s + before;
-}
-
-// grid (nblk, nb): bsum[b * nblk + blk] = the sum of column b's lengths over workgroup blk's records
-__global__ void __launch_bounds__(kScanThreads) k_tag_sums(const int64_t *__restrict__ off, int64_t ostride, int64_t n,
-                                                           int64_t nblk, int64_t *__restrict__ bsum) {
-  __shared__ int64_t ws[kScanThreads / 64];
-  const int64_t k = (int64_t)blockIdx.x * kScanThreads + threadIdx.x;
-  int64_t total;
-  block_scan1(k < n ? off[blockIdx.y * ostride + k] : 0, &total, ws);
-  if (threadIdx.x == 0) bsum[blockIdx.y * nblk + blockIdx.x] = total;
-}
-
-// one workgroup per column: its sums -> exclusive prefix sums in place, totals[b] = the column's bytes
-__global__ void __launch_bounds__(kScanThreads) k_tag_scan_sums(int64_t nblk, int64_t *__restrict__ bsum,
-                                                                int64_t *__restrict__ totals) {
-  __shared__ int64_t ws[kScanThreads / 64];
-  int64_t *col = bsum + blockIdx.x * nblk;
-  int64_t run = 0;
-  for (int64_t b0 = 0; b0 < nblk; b0 += kScanThreads) {
-    const int64_t b = b0 + threadIdx.x;
-    const int64_t v = b < nblk ? col[b] : 0;
-    int64_t total;
-    const int64_t incl = block_scan1(v, &total, ws);
-    if (b < nblk) col[b] = run + incl - v;
-    run += total;
-  }
-  if (threadIdx.x == 0) totals[blockIdx.x] = run;
-}
-
-// grid (nblk, nb): column b's lengths -> exclusive prefix sums in place, [n] = its total
-__global__ void __launch_bounds__(kScanThreads) k_tag_offsets(int64_t *__restrict__ off, int64_t ostride, int64_t n,
-                                                              int64_t nblk, const int64_t *__restrict__ bsum) {
-  __shared__ int64_t ws[kScanThreads / 64];
-  const int64_t k = (int64_t)blockIdx.x * kScanThreads + threadIdx.x;
-  int64_t *col = off + blockIdx.y * ostride;
-  const int64_t v = k < n ? col[k] : 0;
-  int64_t total;
-  const int64_t e = bsum[blockIdx.y * nblk + blockIdx.x] + block_scan1(v, &total, ws);
-  if (k >= n) return;
-  col[k] = e - v;
-  if (k == n - 1) col[n] = e;
-}
-
 }  // namespace
 
 int tag_long_aux_bytes() { return sbam_tag::kLongAuxBytes; }
-int64_t tag_scan_blocks(int64_t n) { return (n + kScanThreads - 1) / kScanThreads; }
 
 hipError_t launch_tag_walk(const TagWalkArgs &a, hipStream_t s) {
   if (a.rec.n <= 0) return hipSuccess;
   const int64_t nblk = (a.rec.n + kWalkThreads - 1) / kWalkThreads;
   hipLaunchKernelGGL(k_tag_walk, dim3((unsigned)nblk), dim3(kWalkThreads), (size_t)a.nq * kWalkThreads * sizeof(uint16_t),
                      s, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_tag_scan(int64_t *off, int64_t ostride, int64_t n, int32_t nb, int64_t *bsum, int64_t *totals,
-                           hipStream_t s) {
-  if (n <= 0 || nb <= 0) return hipSuccess;
-  const int64_t nblk = tag_scan_blocks(n);
-  hipLaunchKernelGGL(k_tag_sums, dim3((unsigned)nblk, (unsigned)nb), dim3(kScanThreads), 0, s, off, ostride, n, nblk,
-                     bsum);
-  hipLaunchKernelGGL(k_tag_scan_sums, dim3((unsigned)nb), dim3(kScanThreads), 0, s, nblk, bsum, totals);
-  hipLaunchKernelGGL(k_tag_offsets, dim3((unsigned)nblk, (unsigned)nb), dim3(kScanThreads), 0, s, off, ostride, n, nblk,
-                     bsum);
   return hipGetLastError();
 }
 

@@ -271,6 +271,8 @@ _SIGNATURES = {  # (restype, argtypes) of every symbol include/sbam.h declares
                                          _P(_i64)]),
     "sbam_write_bai": (ctypes.c_int, [_vp, _vp, _i64, _P(_i64)]),
     "sbam_index_long_cigar_ops": (ctypes.c_int, []),
+    "sbam_test_exclusive_scan": (ctypes.c_int, [ctypes.c_int, _vp, _i64, _i32, _vp]),
+    "sbam_test_scan_sums_int": (ctypes.c_int, [ctypes.c_int, _vp, _i64, _vp]),
     "sbam_last_kernel_ms": (ctypes.c_double, [_vp, ctypes.c_char_p]),
 }
 EXPORTS = list(_SIGNATURES)
