@@ -271,6 +271,18 @@ typedef struct {
 int sbam_load_records(sbam_ctx *ctx, const sbam_split_args *args, int64_t first, int64_t count, int64_t *split_counts,
                       int64_t *n_records);
 
+/* Which way the last sbam_split_records / sbam_compute_splits / sbam_load_records took to its record counts
+ * (read-only; no reference counterpart: RecordStream only ever walks):
+ *   *tried             1 when a success bitmap covered the splits and use_success_bitmap asked for it;
+ *   *proved            1 when the chain proof held and the counts (and record lists) came from the bitmap, 0 when the
+ *                      chains were walked;
+ *   *missing_links,    the list-form chain pass's counters for the check that left that bitmap: PASS0 positions whose
+ *   *failed_fallbacks  hop is not the next PASS0 position, and fallback walks that failed.  -1 when the bitmap was not
+ *                      tried or not list-form, or when a later check ran before this call asked for them.
+ * Any pointer may be NULL. */
+int sbam_records_path(sbam_ctx *ctx, int32_t *tried, int32_t *proved, int64_t *missing_links,
+                      int64_t *failed_fallbacks);
+
 /* Copy records [i0, i0+n) of the last sbam_load_records into caller-owned host columns. */
 int sbam_get_record_columns(sbam_ctx *ctx, int64_t i0, int64_t n, const sbam_record_columns *out);
 
@@ -482,6 +494,18 @@ int sbam_test_exclusive_scan(int device, const int64_t *in, int64_t n, int32_t c
 /* One workgroup's scan of n per-workgroup sums (the step between the passes of a device-wide scan; BGZF chunk counts,
  * MetadataStream.scala:23-54): out receives n exclusive prefix sums as int64 and, at [n], the total. */
 int sbam_test_scan_sums_int(int device, const int32_t *in, int64_t n, int64_t *out);
+/* The record-chain proof, the split popcounts and the split offsets (RecordStream.scala:27-41 read off a success
+ * bitmap) on inputs of the caller's: a stream u of L bytes (copied with the library's zero pad behind it), a bitmap of
+ * n_words words whose bit 0 is stream offset xa (a multiple of 64), the proof range [X0, X1) and n_splits chains
+ * [xs[i], xe[i]) (xs < 0 or xs >= xe: an empty split), all inside the bitmap (else SBAM_ERR_ARG).  list / exact (both
+ * or neither): an ascending PASS0 list of n_list offsets and the chain pass's three counter words.  fail[0] receives
+ * the proof's flag, fail[1] the popcounts' (a split whose first offset is not a set bit); counts[n_splits] the record
+ * counts, *n_offsets their sum, and offsets (cap entries) the set bits of every split at the exclusive scan of the
+ * counts. */
+int sbam_test_chain_proof(int device, const uint8_t *u, int64_t L, const uint64_t *bm, int64_t n_words, int64_t xa,
+                          int64_t X0, int64_t X1, const int64_t *xs, const int64_t *xe, int64_t n_splits,
+                          const int64_t *list, int64_t n_list, const uint64_t *exact, int32_t *fail, int64_t *counts,
+                          int64_t *offsets, int64_t cap, int64_t *n_offsets);
 
 /* ---- timing support for bench/profiling -------------------------------------------------------- */
 /* Device time (ms, HIP events on the library's stream) of the most recent launch of a named kernel

@@ -240,6 +240,11 @@ struct sbam_ctx {
   DevBuf<unsigned long long> d_nfb;
   // split chains: per-split first record / chain end / count / record base
   DevBuf<int64_t> d_sx, d_se, d_sn, d_sb;
+  // what the last split_counts did (sbam_records_path): bitmap tried, proof held, and the list pass's link counters
+  // (-1: not list-form), which stay in d_nfb until asked for (rp_fetch) or until the next check replaces them
+  int32_t rp_tried = 0, rp_proved = 0;
+  int64_t rp_missing = -1, rp_failed = -1;
+  bool rp_fetch = false;
   // decoded records of the last sbam_load_records (offset column + RecordColumnsDev in one arena)
   DevBuf<int64_t> d_roff;
   DevBuf<uint8_t> d_rcols;
@@ -331,7 +336,7 @@ void set_bitmap(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, bool list_form) 
   c->bm_list = list_form;
   c->bm_valid = true;
 }
-void drop_bitmap(sbam_ctx *c) { c->bm_valid = c->bm_list = false; }
+void drop_bitmap(sbam_ctx *c) { c->bm_valid = c->bm_list = c->rp_fetch = false; }
 
 // The stages a context can hold: candidates, block table, stream (with its bitmap), records (with their fields).
 bool any_stage_ran(const sbam_ctx *c) { return c->ncand >= 0 || c->blk.n >= 0 || c->L >= 0 || c->n_loaded >= 0; }
@@ -1329,6 +1334,9 @@ static int split_counts(sbam_ctx *c, bool try_bitmap, const std::vector<int64_t>
   const int64_t n = (int64_t)xs.size();
   *proved = false;
   cnt.assign(n, 0);
+  c->rp_tried = c->rp_proved = 0;
+  c->rp_missing = c->rp_failed = -1;
+  c->rp_fetch = false;
   if (!n) return SBAM_OK;
   HIPCHK(c, c->d_sx.ensure(n));
   HIPCHK(c, c->d_se.ensure(n));
@@ -1354,7 +1362,10 @@ static int split_counts(sbam_ctx *c, bool try_bitmap, const std::vector<int64_t>
     HIPCHK(c, hipMemcpyAsync(&fail, d_fail, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(cnt.data(), c->d_sn, n * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->rp_tried = 1;
+    c->rp_fetch = c->bm_list;
     if (!fail) {
+      c->rp_proved = 1;
       *proved = true;
       return SBAM_OK;
     }
@@ -1489,6 +1500,25 @@ int sbam_load_records(sbam_ctx *c, const sbam_split_args *a, int64_t first, int6
   if (split_counts_out)
     for (int64_t i = 0; i < count; i++) split_counts_out[i] = cnt[i];
   if (n_records) *n_records = N;
+  return SBAM_OK;
+}
+
+int sbam_records_path(sbam_ctx *c, int32_t *tried, int32_t *proved, int64_t *missing_links,
+                      int64_t *failed_fallbacks) {
+  if (!c) return SBAM_ERR_ARG;
+  if (c->rp_fetch) {  // the counters of the check whose bitmap that call used are still in d_nfb
+    unsigned long long h[3] = {0, 0, 0};
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(h, c->d_nfb, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->rp_missing = (int64_t)h[1];
+    c->rp_failed = (int64_t)h[2];
+    c->rp_fetch = false;
+  }
+  if (tried) *tried = c->rp_tried;
+  if (proved) *proved = c->rp_proved;
+  if (missing_links) *missing_links = c->rp_missing;
+  if (failed_fallbacks) *failed_fallbacks = c->rp_failed;
   return SBAM_OK;
 }
 
@@ -2042,6 +2072,91 @@ int sbam_test_scan_sums_int(int device, const int32_t *in, int64_t n, int64_t *o
   if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (N + 1) * 8, hipMemcpyDeviceToHost, t.stream);
   if (e == hipSuccess) e = hipStreamSynchronize(t.stream);
   return e == hipSuccess ? SBAM_OK : SBAM_ERR_HIP;
+}
+
+// The three record kernels behind split_counts / sbam_load_records' proven path, on a stream, a bitmap and splits
+// of the caller's.  Every index a kernel may form from its arguments is checked here first: the bitmap covers
+// [xa, xa + 64 n_words), [X0, X1) and every split lie inside it, and the stream gets the library's zero pad.
+int sbam_test_chain_proof(int device, const uint8_t *u, int64_t L, const uint64_t *bm, int64_t n_words, int64_t xa,
+                          int64_t X0, int64_t X1, const int64_t *xs, const int64_t *xe, int64_t n_splits,
+                          const int64_t *list, int64_t n_list, const uint64_t *exact, int32_t *fail, int64_t *counts,
+                          int64_t *offsets, int64_t cap, int64_t *n_offsets) {
+  if (L < 0 || n_words < 1 || n_splits < 0 || n_list < 0 || cap < 0 || !bm || !fail || !n_offsets) return SBAM_ERR_ARG;
+  if ((L && !u) || (n_splits && (!xs || !xe || !counts)) || (cap && !offsets)) return SBAM_ERR_ARG;
+  if ((list != nullptr) != (exact != nullptr) || (n_list && !list)) return SBAM_ERR_ARG;
+  const int64_t xb = xa + 64 * n_words;
+  if (xa < 0 || (xa & 63) || X0 < xa || X1 > xb) return SBAM_ERR_ARG;
+  const size_t S = (size_t)n_splits;
+  int64_t worst = 0;  // most offsets k_split_offsets can write for one split: the set bits of its range
+  for (size_t i = 0; i < S; i++) {
+    if (xs[i] < 0 || xs[i] >= xe[i]) continue;
+    if (xs[i] < xa || xe[i] > xb) return SBAM_ERR_ARG;
+    int64_t pc = 0;
+    for (int64_t w = (xs[i] - xa) >> 6; w <= (xe[i] - 1 - xa) >> 6; w++) pc += __builtin_popcountll(bm[w]);
+    worst = std::max(worst, pc);
+  }
+  for (int64_t i = 1; i < n_list; i++)
+    if (list[i] < list[i - 1]) return SBAM_ERR_ARG;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t nblk = (size_t)exclusive_scan_blocks(n_splits);
+  const size_t o_u = 0, o_bm = o_u + up((size_t)L + kStreamPad), o_xs = o_bm + up((size_t)n_words * 8),
+               o_xe = o_xs + up(S * 8 + 8), o_cnt = o_xe + up(S * 8 + 8), o_base = o_cnt + up(S * 8 + 8),
+               o_bsum = o_base + up((S + 1) * 8), o_tot = o_bsum + up(nblk * 8 + 8), o_list = o_tot + 256,
+               o_exact = o_list + up((size_t)n_list * 8 + 8), o_fail = o_exact + 256, o_end = o_fail + 256;
+  ScanTest t;
+  if (t.open(device, o_end) != hipSuccess) return SBAM_ERR_HIP;
+  uint8_t *d_u = t.buf + o_u;
+  auto *d_bm = reinterpret_cast<unsigned long long *>(t.buf + o_bm);
+  auto *d_xs = reinterpret_cast<int64_t *>(t.buf + o_xs), *d_xe = reinterpret_cast<int64_t *>(t.buf + o_xe);
+  auto *d_cnt = reinterpret_cast<int64_t *>(t.buf + o_cnt), *d_base = reinterpret_cast<int64_t *>(t.buf + o_base);
+  auto *d_bsum = reinterpret_cast<int64_t *>(t.buf + o_bsum), *d_tot = reinterpret_cast<int64_t *>(t.buf + o_tot);
+  auto *d_list = reinterpret_cast<int64_t *>(t.buf + o_list);
+  auto *d_exact = reinterpret_cast<unsigned long long *>(t.buf + o_exact);
+  auto *d_fail = reinterpret_cast<int32_t *>(t.buf + o_fail);
+  hipStream_t s = t.stream;
+#define T_(expr) do { if ((expr) != hipSuccess) return SBAM_ERR_HIP; } while (0)
+  T_(hipMemsetAsync(t.buf, 0, o_end, s));
+  if (L) T_(hipMemcpyAsync(d_u, u, (size_t)L, hipMemcpyHostToDevice, s));
+  T_(hipMemcpyAsync(d_bm, bm, (size_t)n_words * 8, hipMemcpyHostToDevice, s));
+  if (S) {
+    T_(hipMemcpyAsync(d_xs, xs, S * 8, hipMemcpyHostToDevice, s));
+    T_(hipMemcpyAsync(d_xe, xe, S * 8, hipMemcpyHostToDevice, s));
+    T_(hipMemsetAsync(d_cnt, 0xff, S * 8, s));
+  }
+  if (n_list) T_(hipMemcpyAsync(d_list, list, (size_t)n_list * 8, hipMemcpyHostToDevice, s));
+  if (exact) T_(hipMemcpyAsync(d_exact, exact, 24, hipMemcpyHostToDevice, s));
+  // fail[0]: the proof; fail[1]: a split whose first record is not a set bit (one word in split_counts)
+  T_(launch_chain_proof(d_u, L, d_bm, xa, X0, X1, d_fail, exact ? d_exact : nullptr, s));
+  T_(launch_split_popcounts(d_bm, xa, d_xs, d_xe, n_splits, d_cnt, d_fail + 1, list ? d_list : nullptr, n_list,
+                            exact ? d_exact : nullptr, s));
+  T_(hipMemcpyAsync(fail, d_fail, 8, hipMemcpyDeviceToHost, s));
+  if (S) T_(hipMemcpyAsync(counts, d_cnt, S * 8, hipMemcpyDeviceToHost, s));
+  T_(hipStreamSynchronize(s));
+  int64_t total = 0;
+  for (size_t i = 0; i < S; i++) {
+    if (counts[i] < 0) return SBAM_ERR_STATE;
+    total += counts[i];
+  }
+  *n_offsets = total;
+  if (!S) return SBAM_OK;
+  // bases = the exclusive scan of the counts, as sbam_load_records takes them; room for the counts' total plus one
+  // split's set bits, so a count that disagrees with the bitmap still writes inside the buffer
+  T_(hipMemcpyAsync(d_base, d_cnt, S * 8, hipMemcpyDeviceToDevice, s));
+  T_(launch_exclusive_scan(d_base, (int64_t)S + 1, n_splits, 1, d_bsum, d_tot, s));
+  int64_t *d_out = nullptr;
+  const size_t n_out = (size_t)(total + worst + 1);
+  T_(hipMalloc(reinterpret_cast<void **>(&d_out), n_out * 8));
+  hipError_t e = hipMemsetAsync(d_out, 0xff, n_out * 8, s);
+  if (e == hipSuccess) e = launch_split_offsets(d_bm, xa, d_xs, d_xe, d_base, n_splits, d_out, s);
+  int64_t dev_total = -1;
+  if (e == hipSuccess) e = hipMemcpyAsync(&dev_total, d_tot, 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && std::min(total, cap) > 0)
+    e = hipMemcpyAsync(offsets, d_out, (size_t)std::min(total, cap) * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(d_out);
+#undef T_
+  if (e != hipSuccess) return SBAM_ERR_HIP;
+  return dev_total == total ? SBAM_OK : SBAM_ERR_STATE;
 }
 
 }  // extern "C"

@@ -382,7 +382,8 @@ __global__ __launch_bounds__(256) void k_p0_links(StreamView sv, const int64_t *
     const int64_t c_end = p + 36 + (lrn >= 2 ? lrn : 0) + 4 * (int64_t)nc;
     const int64_t nxt = p + 4 + (int64_t)bs;
     const bool link = i + 1 < n ? list[i + 1] == nxt : (nxt >= x1 && nxt <= sv.L);
-    ok[i] = (link && nxt > c_end) ? 1 : 0;
+    // (nxt == c_end, a record that ends with its name and CIGAR, leaves walk_chain's cursor on nxt as well)
+    ok[i] = (link && nxt >= c_end) ? 1 : 0;
   }
 }
 

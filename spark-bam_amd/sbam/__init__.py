@@ -255,6 +255,7 @@ _SIGNATURES = {  # (restype, argtypes) of every symbol include/sbam.h declares
     "sbam_reserve": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64]),
     "sbam_record_spans": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "sbam_load_records": (ctypes.c_int, [_vp, _P(_SplitArgs), _i64, _i64, _vp, _P(_i64)]),
+    "sbam_records_path": (ctypes.c_int, [_vp, _P(_i32), _P(_i32), _P(_i64), _P(_i64)]),
     "sbam_get_record_columns": (ctypes.c_int, [_vp, _i64, _i64, _P(_RecordColumns)]),
     "sbam_record_columns_device": (ctypes.c_int, [_vp, _P(_RecordColumns), _P(_i64)]),
     "sbam_load_record_fields": (ctypes.c_int, [_vp, _i64, _i64, ctypes.c_uint32, _P(_RecordFieldTotals)]),
@@ -273,6 +274,8 @@ _SIGNATURES = {  # (restype, argtypes) of every symbol include/sbam.h declares
     "sbam_index_long_cigar_ops": (ctypes.c_int, []),
     "sbam_test_exclusive_scan": (ctypes.c_int, [ctypes.c_int, _vp, _i64, _i32, _vp]),
     "sbam_test_scan_sums_int": (ctypes.c_int, [ctypes.c_int, _vp, _i64, _vp]),
+    "sbam_test_chain_proof": (ctypes.c_int, [ctypes.c_int, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp,
+                                             _i64, _vp, _vp, _vp, _vp, _i64, _P(_i64)]),
     "sbam_last_kernel_ms": (ctypes.c_double, [_vp, ctypes.c_char_p]),
 }
 EXPORTS = list(_SIGNATURES)
@@ -816,6 +819,16 @@ class BamFile:
         rc = _RecordColumns(**{k: v.ctypes.data for k, v in cols.items()})
         self._check(self.L.sbam_get_record_columns(self.ctx, 0, n.value, ctypes.byref(rc)))
         return sizes, cols
+
+    def records_path(self) -> dict:
+        """What the last split_records / compute_splits / load_records did (sbam_records_path): `tried` the success
+        bitmap, `proved` the chains equal to it; `missing_links` / `failed_fallbacks` of the list-form chain pass
+        behind that bitmap (-1: no such bitmap, or a later check ran first)."""
+        t, p, m, f = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(-1), ctypes.c_int64(-1)
+        self._check(self.L.sbam_records_path(self.ctx, ctypes.byref(t), ctypes.byref(p), ctypes.byref(m),
+                                             ctypes.byref(f)))
+        return {"tried": bool(t.value), "proved": bool(p.value), "missing_links": int(m.value),
+                "failed_fallbacks": int(f.value)}
 
     def load_record_fields(self, i0: int = 0, n: Optional[int] = None,
                            fields: Sequence[str] = ("name", "cigar", "seq", "qual", "aux"), host: bool = True):
