@@ -486,6 +486,59 @@ int sbam_write_bai(sbam_ctx *ctx, uint8_t *out, int64_t cap, int64_t *n_bytes);
  * no reference counterpart, Index.scala:53-90 only reads): for tests that must reach that path. */
 int sbam_index_long_cigar_ops(void);
 
+/* ---- BAM writer: records of the last sbam_load_records -> BGZF bytes on the device ------------------------------
+ * htsjdk-rewrite (cli/src/main/scala/org/hammerlab/bam/rewrite/HTSJDKRewrite.scala:21-91): the BAM header, then the
+ * selected records back to back, cut every block_bytes uncompressed bytes (htsjdk's 65498), each piece deflated and
+ * framed as a BGZF block, the 28-byte EOF block last.  The uncompressed side equals the reference writer's byte for
+ * byte; the compressed bytes are this library's own (level 0: stored blocks; level 1: LZ77 + the fixed Huffman code,
+ * with a stored block wherever that would be smaller), deterministic for equal inputs and arguments. */
+typedef struct {
+  const int64_t *range_lo;   /* host: record-index ranges [lo, hi) into the last sbam_load_records (HTSJDKRewrite.scala's */
+  const int64_t *range_hi;   /* -r read-index ranges), ascending and disjoint                                         */
+  int64_t n_ranges;          /* 0: every record                                                                       */
+  const uint8_t *keep_device;/* optional device byte per loaded record; nonzero = keep; ANDed with the ranges         */
+  int32_t level;             /* 0 stored, 1 LZ77 + fixed Huffman                                                      */
+  int32_t block_bytes;       /* uncompressed bytes per block, 1..65498; 0 = 65498                                     */
+  int32_t with_header;       /* 1: the BAM header (stream bytes [0, header end)) goes first; needs a context that
+                                starts at file offset 0 and has read its header (sbam_header)                         */
+  int32_t with_eof;          /* 1: append the 28-byte EOF block                                                       */
+} sbam_write_args;
+typedef struct {
+  int64_t n_records;        /* records written */
+  int64_t header_bytes;     /* 0 without with_header */
+  int64_t ubytes;           /* uncompressed bytes written: header_bytes + the records' 4 + block_size */
+  int64_t n_blocks;         /* data blocks (the EOF block is not counted) */
+  int64_t n_stored_blocks;  /* of them in the stored form */
+  int64_t comp_bytes;       /* bytes of the file, the EOF block included */
+} sbam_write_totals;
+
+/* Write the selected records (HTSJDKRewrite.scala:52-76: header, then every read inside the ranges).  with_header = 0
+ * and with_eof = 0 exist so that the outputs of a file's shards concatenate into one valid BAM.  SBAM_ERR_STATE: no
+ * sbam_load_records has run, or with_header on a context that does not start at offset 0 (or whose header has not been
+ * read); SBAM_ERR_ARG: ranges out of order, overlapping or past the loaded records, level not 0 or 1, block_bytes
+ * outside 0..65498.  The file bytes, the block table and the records' positions stay on the device, owned by ctx
+ * (grow-only buffers: the stream at its size, the file at its stored bound of ubytes + 31 per block + 28, the deflate
+ * slots at one batch of 4096 blocks), until the next sbam_write_bam, load, reset or close. */
+int sbam_write_bam(sbam_ctx *ctx, const sbam_write_args *args, sbam_write_totals *totals);
+/* The file bytes of the last sbam_write_bam (what HTSJDKRewrite.scala:52-76 leaves at its output path); cap smaller
+ * than comp_bytes: SBAM_ERR_ARG. */
+int sbam_get_written(sbam_ctx *ctx, uint8_t *out, int64_t cap);
+/* The same bytes on the device (HTSJDKRewrite.scala:52-76): *dev stays valid until the next write, load or close. */
+int sbam_written_device(sbam_ctx *ctx, const uint8_t **dev, int64_t *n);
+/* The written data blocks (HTSJDKRewrite.scala:78-83 -b, the .blocks sidecar's start, compressed size, uncompressed
+ * size), n_blocks entries each.  A NULL member is not copied. */
+int sbam_get_written_blocks(sbam_ctx *ctx, int64_t *start, int32_t *csize, int32_t *usize);
+/* Pos of every written record in the new file (HTSJDKRewrite.scala:85-90 -i, the .records sidecar), n_records entries
+ * each, in writing order. */
+int sbam_get_written_records(sbam_ctx *ctx, int64_t *block_pos, int32_t *block_off);
+
+/* ---- for tests: the writer's deflate and framing over arbitrary bytes (HTSJDKRewrite.scala:52-76's
+ * BlockCompressedOutputStream half; no context: the call allocates its device buffers, runs on a stream of its own,
+ * copies back and frees).  in[0, n) is cut every block_bytes (0 = 65498); out receives the BGZF bytes, *n_out their
+ * count (cap too small: SBAM_ERR_ARG with *n_out set), *n_stored_blocks (may be NULL) the blocks in the stored form. */
+int sbam_test_deflate(int device, const uint8_t *in, int64_t n, int32_t block_bytes, int32_t level, int32_t with_eof,
+                      uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_stored_blocks);
+
 /* ---- for tests: the library's prefix-sum primitives (no reference counterpart; no context: each call allocates its
  * device buffers, runs on a stream of its own, copies back and frees) ------------------------------------------- */
 /* The in-place exclusive scan behind every offsets column (SAM spec §4.2's variable-length fields as CSR offsets):
@@ -512,7 +565,9 @@ int sbam_test_chain_proof(int device, const uint8_t *u, int64_t L, const uint64_
  * family: "scan", "inflate", "check_full", "check_eager", "records", "load_records", "record_fields" (the gather of
  * sbam_load_record_fields; "record_field_sizes": its sizes and scan), "index" (sbam_build_index, from its first pass
  * through the linear index's fill), "crc" (the block CRC32 check), "record_tags" (sbam_load_record_tags: its walk and
- * scans, "record_tag_walk", plus the gather of its byte columns, "record_tag_bytes"). Returns -1 if none. */
+ * scans, "record_tag_walk", plus the gather of its byte columns, "record_tag_bytes"), "write_select", "write_gather",
+ * "write_deflate", "write_frame" (sbam_write_bam's stages; deflate and frame: of its last batch of blocks). Returns -1
+ * if none. */
 double sbam_last_kernel_ms(sbam_ctx *ctx, const char *kernel);
 
 #ifdef __cplusplus

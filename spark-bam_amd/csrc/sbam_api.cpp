@@ -11,9 +11,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
+#include "sbam_deflate_core.h"
 #include "sbam_internal.h"
 #include "sbam_tag_core.h"
 
@@ -80,6 +82,20 @@ struct TokArena {
   DevBuf<uint8_t> buf;
   size_t usable() const { return buf.size() ? buf.size() - 1024 : 0; }
   hipError_t ensure(size_t bytes, bool *grew = nullptr) { return buf.ensure(bytes + 1024, grew); }
+};
+
+// The BAM writer's blocks stage (sbam_write.hip): an uncompressed stream in, BGZF bytes and their block table out.
+// Owned by a context (sbam_write_bam) or by a test call (sbam_test_deflate); writer_run fills it.
+constexpr int64_t kWriteBatch = 4096;  // blocks deflated into the slots at a time (268 MB of stream at 65 498)
+struct Writer {
+  DevBuf<uint8_t> u;      // the stream (writer_ensure_stream)
+  DevBuf<uint8_t> slots;  // one batch's fixed-Huffman payloads
+  DevBuf<int32_t> cols;   // by block: payload bytes | stored | csize | usize
+  DevBuf<int64_t> start;  // by block, + the end offset
+  DevBuf<int64_t> tsz;    // the batch's size column, its scan's scratch and total, the stored-block counter
+  DevBuf<uint8_t> file;
+  int64_t ubytes = -1, nb = 0, n_stored = 0, comp_bytes = 0;  // of the last run (ubytes -1: none)
+  int32_t block_bytes = 0;
 };
 
 // Host mirror of the scanned block table (relative offsets).  The fast scan's table comes back behind the GPU, into
@@ -276,6 +292,12 @@ struct sbam_ctx {
   bool idx_built = false;
   sbam_index_totals idx_tot{};
   std::vector<int64_t> idx_intv;  // n_ref + 1 window offsets
+  // BAM of the last sbam_write_bam: the selection's columns (length / offset, 0-1 / ordinal, source position, scan
+  // scratch, totals), the ranges, the gather's tiles, the blocks stage, and the written records' Pos columns
+  DevBuf<int64_t> d_wsel, d_wrange, d_wtiles, d_wrpos;
+  DevBuf<int32_t> d_wroff;
+  Writer w;
+  sbam_write_totals w_tot{};
   // small device scratch
   DevBuf<int64_t> d_small;  // 64 int64
   DevBuf<unsigned long long> d_counts;
@@ -350,6 +372,7 @@ hipError_t drop_stages(sbam_ctx *c) {
   c->n_loaded = -1;
   c->f_n = c->t_n = -1;
   c->loaded_all = c->idx_built = false;
+  c->w.ubytes = -1;
   return e;
 }
 
@@ -421,6 +444,80 @@ hipError_t ensure_index(sbam_ctx *c, size_t N, bool *grew = nullptr) {
   HIPTRY(c->d_iend.ensure(N, grew));
   HIPTRY(c->d_ibin.ensure(N, grew));
   return c->d_iheads.ensure((size_t)index_blocks((int64_t)N) + 1, grew);
+}
+
+// The BAM writer.  Its scratch is bounded by the batch, its results by what they hold:
+//   w.u      the stream, rounded up to the gather's 8-byte stores, + kWritePad
+//   w.slots  min(blocks, kWriteBatch) slots of write_slot_stride(block_bytes) bytes (the stored bound + 8, not 64 KiB),
+//            + 16: only level 1 uses them
+//   w.cols   four int32 per block; w.start one int64 per block + 1
+//   w.tsz    kWriteBatch + 1 sizes | the scan's per-workgroup sums | its total | the stored-block counter
+//   w.file   the stored bound: ubytes + 31 per block (18 + 5 + 8) + 28; a fixed-Huffman block is never larger
+int64_t write_blocks(int64_t ubytes, int32_t block_bytes) { return (ubytes + block_bytes - 1) / block_bytes; }
+hipError_t ensure_write_stream(Writer &w, int64_t ubytes) {
+  return w.u.ensure((((size_t)ubytes + 7) & ~(size_t)7) + kWritePad);
+}
+hipError_t ensure_write_blocks(Writer &w, int64_t ubytes, int32_t block_bytes, int32_t level) {
+  const int64_t nb = write_blocks(ubytes, block_bytes), batch = std::min(nb, kWriteBatch);
+  if (level) HIPTRY(w.slots.ensure((size_t)(batch * write_slot_stride(block_bytes) + 16)));
+  HIPTRY(w.cols.ensure((size_t)(4 * nb)));
+  HIPTRY(w.start.ensure((size_t)(nb + 1)));
+  HIPTRY(w.tsz.ensure((size_t)(kWriteBatch + 1 + exclusive_scan_blocks(kWriteBatch) + 2)));
+  return w.file.ensure((size_t)(ubytes + 31 * nb + 28));
+}
+// the selection over N loaded records: two columns of N + 2, the sources (N + 1), the scan's sums, two totals
+struct WriteSelLayout {
+  size_t stride, src, bsum, tot, words;
+};
+WriteSelLayout write_sel_layout(size_t N) {
+  WriteSelLayout l;
+  l.stride = N + 2;
+  l.src = 2 * l.stride;
+  l.bsum = l.src + N + 1;
+  l.tot = l.bsum + 2 * (size_t)exclusive_scan_blocks((int64_t)N + 1);
+  l.words = l.tot + 2;
+  return l;
+}
+
+// Deflate and frame w.u[0, ubytes) into w.file, a batch of blocks at a time; the host reads each batch's size (8 bytes)
+// to place the next.  tc: the context whose timers record the stages (nullptr: none).
+hipError_t writer_run(Writer &w, hipStream_t s, sbam_ctx *tc, int64_t ubytes, int32_t block_bytes, int32_t level,
+                      bool with_eof) {
+  w.ubytes = -1;
+  HIPTRY(ensure_write_blocks(w, ubytes, block_bytes, level));
+  const int64_t nb = write_blocks(ubytes, block_bytes);
+  int32_t *pay = w.cols, *stored = pay + nb, *csize = stored + nb, *usize = csize + nb;
+  int64_t *bsum = w.tsz + kWriteBatch + 1, *tot = bsum + exclusive_scan_blocks(kWriteBatch);
+  unsigned long long *n_stored = reinterpret_cast<unsigned long long *>(tot + 1);
+  HIPTRY(hipMemsetAsync(n_stored, 0, 8, s));
+  int64_t base = 0, b0 = 0;
+  do {
+    const int64_t k = std::min(kWriteBatch, nb - b0);
+    const WriteBlocksArgs a{w.u, ubytes, block_bytes, b0, k, w.slots, write_slot_stride(block_bytes), pay, stored, w.tsz};
+    {
+      std::unique_ptr<Timer> t(tc ? new Timer(tc, "write_deflate") : nullptr);
+      HIPTRY(launch_write_deflate(a, level, s));
+    }
+    {
+      std::unique_ptr<Timer> t(tc ? new Timer(tc, "write_frame") : nullptr);
+      HIPTRY(launch_exclusive_scan(w.tsz, k + 1, k, 1, bsum, tot, s));
+      const WriteFrameArgs f{w.file, base, (with_eof && b0 + k >= nb) ? 1 : 0, w.start, csize, usize, n_stored};
+      HIPTRY(launch_write_frame(a, f, s));
+    }
+    int64_t bytes = 0;
+    HIPTRY(hipMemcpyAsync(&bytes, tot, 8, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipStreamSynchronize(s));
+    base += bytes;
+    b0 += k;
+  } while (b0 < nb);
+  unsigned long long ns = 0;
+  HIPTRY(hipMemcpy(&ns, n_stored, 8, hipMemcpyDeviceToHost));
+  w.ubytes = ubytes;
+  w.nb = nb;
+  w.n_stored = (int64_t)ns;
+  w.comp_bytes = base + (with_eof ? 28 : 0);
+  w.block_bytes = block_bytes;
+  return hipSuccess;
 }
 
 // Typed tags of n records, nq query entries, nb of them with a byte column.  Every piece is 256-B aligned.
@@ -2022,6 +2119,108 @@ int sbam_write_bai(sbam_ctx *c, uint8_t *out, int64_t cap, int64_t *n_bytes) {
   return SBAM_OK;
 }
 
+// ---- BAM writer (htsjdk-rewrite, cli/.../bam/rewrite/HTSJDKRewrite.scala:21-91) ---------------------------------
+int sbam_write_bam(sbam_ctx *c, const sbam_write_args *a, sbam_write_totals *totals) {
+  if (!c || !a) return SBAM_ERR_ARG;
+  if (c->n_loaded < 0 || c->L < 0) return set_err(c, SBAM_ERR_STATE, "sbam_load_records has not run");
+  const int64_t N = c->n_loaded;
+  const int32_t bb = a->block_bytes == 0 ? sbam_deflate::kMaxBlockBytes : a->block_bytes;
+  if (bb < 1 || bb > sbam_deflate::kMaxBlockBytes)
+    return set_err(c, SBAM_ERR_ARG, "block_bytes %d outside 1..%d", (int)a->block_bytes, sbam_deflate::kMaxBlockBytes);
+  if (a->level != 0 && a->level != 1) return set_err(c, SBAM_ERR_ARG, "level %d: 0 (stored) or 1 (fixed Huffman)", (int)a->level);
+  if (a->n_ranges < 0 || (a->n_ranges && (!a->range_lo || !a->range_hi))) return set_err(c, SBAM_ERR_ARG, "ranges missing");
+  for (int64_t r = 0; r < a->n_ranges; r++) {
+    const int64_t lo = a->range_lo[r], hi = a->range_hi[r];
+    if (lo < 0 || hi < lo || hi > N || (r && lo < a->range_hi[r - 1]))
+      return set_err(c, SBAM_ERR_ARG, "range %lld [%lld, %lld): out of order or outside the %lld loaded records",
+                     (long long)r, (long long)lo, (long long)hi, (long long)N);
+  }
+  if (a->with_header && (c->base != 0 || c->header_x < 0))
+    return set_err(c, SBAM_ERR_STATE, "with_header needs a context that starts at file offset 0 and has read its header");
+  HIPCHK(c, hipSetDevice(c->device));
+  c->w.ubytes = -1;
+  const int64_t header_bytes = a->with_header ? c->header_x : 0;
+  const WriteSelLayout sl = write_sel_layout((size_t)N);
+  HIPCHK(c, c->d_wsel.ensure(sl.words));
+  HIPCHK(c, c->d_wrange.ensure((size_t)(2 * a->n_ranges)));
+  int64_t *len = c->d_wsel, *cnt = len + sl.stride, *src = len + sl.src, *bsum = len + sl.bsum, *tot = len + sl.tot;
+  if (a->n_ranges) {
+    HIPCHK(c, hipMemcpyAsync(c->d_wrange, a->range_lo, (size_t)a->n_ranges * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_wrange + a->n_ranges, a->range_hi, (size_t)a->n_ranges * 8, hipMemcpyHostToDevice,
+                             c->stream));
+  }
+  {
+    Timer t(c, "write_select");
+    const WriteSelectArgs sa{c->d_roff, c->rcols.block_size, N, c->L, c->d_wrange, c->d_wrange + a->n_ranges,
+                             a->n_ranges, a->keep_device, header_bytes, len, cnt, src};
+    HIPCHK(c, launch_write_select(sa, c->stream));
+    HIPCHK(c, launch_exclusive_scan(len, (int64_t)sl.stride, N + 1, 2, bsum, tot, c->stream));
+  }
+  int64_t h[2] = {0, 0};
+  HIPCHK(c, hipMemcpyAsync(h, tot, 16, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const int64_t ubytes = h[0], n_records = h[1];
+  HIPCHK(c, ensure_write_stream(c->w, ubytes));
+  HIPCHK(c, c->d_wtiles.ensure((size_t)(2 * field_gather_tiles(ubytes))));
+  {
+    Timer t(c, "write_gather");
+    // every entry is a "field" at src[i] of len[i] bytes: sbam_fields.hip's gather, divided over output bytes
+    const FieldGatherArgs ga{c->d_u, nullptr, nullptr, nullptr, nullptr, len, N + 1, 0, ubytes, c->w.u, c->d_wtiles, src};
+    HIPCHK(c, launch_field_gather(5, ga, c->stream));
+  }
+  HIPCHK(c, writer_run(c->w, c->stream, c, ubytes, bb, a->level, a->with_eof != 0));
+  HIPCHK(c, c->d_wrpos.ensure((size_t)n_records));
+  HIPCHK(c, c->d_wroff.ensure((size_t)n_records));
+  HIPCHK(c, launch_written_records(len, cnt, N, bb, c->w.start, c->d_wrpos, c->d_wroff, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->w_tot = sbam_write_totals{n_records, header_bytes, ubytes, c->w.nb, c->w.n_stored, c->w.comp_bytes};
+  if (totals) *totals = c->w_tot;
+  return SBAM_OK;
+}
+
+int sbam_get_written(sbam_ctx *c, uint8_t *out, int64_t cap) {
+  if (!c || (!out && cap > 0)) return SBAM_ERR_ARG;
+  if (c->w.ubytes < 0) return set_err(c, SBAM_ERR_STATE, "sbam_write_bam has not run");
+  if (cap < c->w.comp_bytes)
+    return set_err(c, SBAM_ERR_ARG, "sbam_get_written: %lld bytes needed, capacity %lld", (long long)c->w.comp_bytes,
+                   (long long)cap);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->w.comp_bytes) HIPCHK(c, hipMemcpy(out, c->w.file, (size_t)c->w.comp_bytes, hipMemcpyDeviceToHost));
+  return SBAM_OK;
+}
+
+int sbam_written_device(sbam_ctx *c, const uint8_t **dev, int64_t *n) {
+  if (!c || !dev || !n) return SBAM_ERR_ARG;
+  if (c->w.ubytes < 0) return set_err(c, SBAM_ERR_STATE, "sbam_write_bam has not run");
+  *dev = c->w.file;
+  *n = c->w.comp_bytes;
+  return SBAM_OK;
+}
+
+int sbam_get_written_blocks(sbam_ctx *c, int64_t *start, int32_t *csize, int32_t *usize) {
+  if (!c) return SBAM_ERR_ARG;
+  if (c->w.ubytes < 0) return set_err(c, SBAM_ERR_STATE, "sbam_write_bam has not run");
+  const size_t nb = (size_t)c->w.nb;
+  if (!nb) return SBAM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int32_t *cs = c->w.cols + 2 * nb, *us = cs + nb;
+  if (start) HIPCHK(c, hipMemcpy(start, c->w.start, nb * 8, hipMemcpyDeviceToHost));
+  if (csize) HIPCHK(c, hipMemcpy(csize, cs, nb * 4, hipMemcpyDeviceToHost));
+  if (usize) HIPCHK(c, hipMemcpy(usize, us, nb * 4, hipMemcpyDeviceToHost));
+  return SBAM_OK;
+}
+
+int sbam_get_written_records(sbam_ctx *c, int64_t *block_pos, int32_t *block_off) {
+  if (!c) return SBAM_ERR_ARG;
+  if (c->w.ubytes < 0) return set_err(c, SBAM_ERR_STATE, "sbam_write_bam has not run");
+  const size_t n = (size_t)c->w_tot.n_records;
+  if (!n) return SBAM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (block_pos) HIPCHK(c, hipMemcpy(block_pos, c->d_wrpos, n * 8, hipMemcpyDeviceToHost));
+  if (block_off) HIPCHK(c, hipMemcpy(block_off, c->d_wroff, n * 4, hipMemcpyDeviceToHost));
+  return SBAM_OK;
+}
+
 // ---- test support: the scan launchers on buffers and a stream of their own (no context) -------------------------
 namespace {
 struct ScanTest {  // a device, a stream and one allocation, released on every path
@@ -2157,6 +2356,33 @@ int sbam_test_chain_proof(int device, const uint8_t *u, int64_t L, const uint64_
 #undef T_
   if (e != hipSuccess) return SBAM_ERR_HIP;
   return dev_total == total ? SBAM_OK : SBAM_ERR_STATE;
+}
+
+// The writer's blocks stage (writer_run: deflate, scan, frame) over the caller's bytes, with the library's pad behind
+// them, on a Writer and a stream of the call's own.
+int sbam_test_deflate(int device, const uint8_t *in, int64_t n, int32_t block_bytes, int32_t level, int32_t with_eof,
+                      uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_stored_blocks) {
+  if (n < 0 || cap < 0 || !n_out || (n && !in) || (cap && !out)) return SBAM_ERR_ARG;
+  const int32_t bb = block_bytes == 0 ? sbam_deflate::kMaxBlockBytes : block_bytes;
+  if (bb < 1 || bb > sbam_deflate::kMaxBlockBytes || (level != 0 && level != 1)) return SBAM_ERR_ARG;
+  if (hipSetDevice(device) != hipSuccess) return SBAM_ERR_HIP;
+  Writer w;  // (freed on every path, with this device current)
+  hipStream_t s = nullptr;
+  if (hipStreamCreate(&s) != hipSuccess) return SBAM_ERR_HIP;
+  hipError_t e = ensure_write_stream(w, n);
+  if (e == hipSuccess) e = hipMemsetAsync(w.u, 0, w.u.size(), s);
+  if (e == hipSuccess && n) e = hipMemcpyAsync(w.u, in, (size_t)n, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = writer_run(w, s, nullptr, n, bb, level, with_eof != 0);
+  int rc = e == hipSuccess ? SBAM_OK : SBAM_ERR_HIP;
+  if (rc == SBAM_OK) {
+    *n_out = w.comp_bytes;
+    if (n_stored_blocks) *n_stored_blocks = w.n_stored;
+    if (cap < w.comp_bytes) rc = SBAM_ERR_ARG;
+    else if (w.comp_bytes && hipMemcpy(out, w.file, (size_t)w.comp_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+      rc = SBAM_ERR_HIP;
+  }
+  (void)hipStreamDestroy(s);
+  return rc;
 }
 
 }  // extern "C"

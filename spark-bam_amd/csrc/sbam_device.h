@@ -52,6 +52,16 @@ SB_DEV T wave_incl_scan(T v) {
   return v;
 }
 
+// the 8 bytes at u + x (u 4-byte aligned, x of any alignment) from the three aligned dwords around them; the buffer is
+// readable for 12 bytes past x rounded down to 4
+SB_DEV uint64_t load8(const uint8_t *u, int64_t x) {
+  const uint32_t *w = reinterpret_cast<const uint32_t *>(u + (x & ~(int64_t)3));
+  const uint32_t s = (uint32_t)(x & 3);
+  const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
+  const uint32_t lo = __builtin_amdgcn_alignbyte(w1, w0, s), hi = __builtin_amdgcn_alignbyte(w2, w1, s);
+  return (uint64_t)lo | ((uint64_t)hi << 32);
+}
+
 // Workgroup inclusive scan of K values per thread (THREADS = blockDim.x; thread order = threadIdx.x): incl[f] = the
 // sum of v[f] over threads 0 .. threadIdx.x, total[f] = over all of them.  ws: THREADS / 64 rows of LDS scratch.
 // Every thread of the workgroup calls it (two barriers).

@@ -70,15 +70,6 @@ __global__ void __launch_bounds__(kSizeThreads) k_field_offsets(FieldSizesArgs a
   }
 }
 
-// the 8 stream bytes at x (any alignment) from the three aligned dwords around them
-SB_DEV uint64_t load8(const uint8_t *u, int64_t x) {
-  const uint32_t *w = reinterpret_cast<const uint32_t *>(u + (x & ~(int64_t)3));
-  const uint32_t s = (uint32_t)(x & 3);
-  const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
-  const uint32_t lo = __builtin_amdgcn_alignbyte(w1, w0, s), hi = __builtin_amdgcn_alignbyte(w2, w1, s);
-  return (uint64_t)lo | ((uint64_t)hi << 32);
-}
-
 // four 4-bit base codes (code j in bits 4j..4j+3) -> four ASCII bytes of "=ACMGRSVTWYHKDBN": the table is four
 // constant dwords; one byte-permute indexes each half with the codes' low three bits, bit 3 selects the half
 SB_DEV uint32_t bases4(uint32_t h) {

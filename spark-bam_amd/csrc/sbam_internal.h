@@ -290,4 +290,46 @@ int64_t exclusive_scan_blocks(int64_t n);
 hipError_t launch_exclusive_scan(int64_t *off, int64_t stride, int64_t n, int32_t cols, int64_t *bsum, int64_t *totals,
                                  hipStream_t s);
 
+
+// BAM writer (sbam_write.hip): select -> (launch_exclusive_scan, launch_field_gather field 5) -> deflate -> frame.
+struct WriteSelectArgs {
+  const int64_t *roff;           // the loaded records' stream offsets and block_size column, n each
+  const int32_t *block_size;
+  int64_t n, L;                  // (L: the stream's length)
+  const int64_t *range_lo, *range_hi;  // device: record-index ranges [lo, hi), ascending and disjoint
+  int64_t n_ranges;              // 0: every record
+  const uint8_t *keep;           // device byte per record (nonzero: keep), or nullptr
+  int64_t header_bytes;          // stream bytes [0, header_bytes) go first (entry 0 of the columns)
+  int64_t *len, *cnt;            // n + 1 values each (room for n + 2: the scan adds the total): bytes and 0 / 1
+  int64_t *src;                  // n + 1: each entry's source position in the stream
+};
+hipError_t launch_write_select(const WriteSelectArgs &a, hipStream_t s);
+// Pos of the written records from the scanned columns (off, ord: n + 2 entries each) and the written block starts
+hipError_t launch_written_records(const int64_t *off, const int64_t *ord, int64_t n, int32_t block_bytes,
+                                  const int64_t *start, int64_t *block_pos, int32_t *block_off, hipStream_t s);
+constexpr int kWritePad = 4096;  // readable bytes behind the writer's stream (the CRC's row lookahead, the matcher's
+                                 // compare past a block's end); the stream is 16-byte aligned
+// One batch of output blocks [b0, b0 + nb): block b holds stream bytes [b * block_bytes, ...) of wu[0, ubytes).
+struct WriteBlocksArgs {
+  const uint8_t *wu;
+  int64_t ubytes;
+  int32_t block_bytes;
+  int64_t b0, nb;
+  uint8_t *slots;        // block b0 + k's fixed-Huffman payload at slots + k * slot_stride (level 1)
+  int64_t slot_stride;   // write_slot_stride(block_bytes): the stored bound, not 64 KiB
+  int32_t *pay, *stored; // by block: payload bytes, 1 = stored form
+  int64_t *tsz;          // by k: 18 + payload + 8; scanned in place (nb + 1 entries) between deflate and frame
+};
+struct WriteFrameArgs {
+  uint8_t *file;         // 8-byte aligned
+  int64_t base;          // file offset of the batch's first block
+  int32_t with_eof;      // the EOF block goes behind the batch
+  int64_t *start;        // by block (+ the end offset behind the batch's last)
+  int32_t *csize, *usize;
+  unsigned long long *n_stored;  // += stored blocks
+};
+int64_t write_slot_stride(int32_t block_bytes);
+hipError_t launch_write_deflate(const WriteBlocksArgs &a, int32_t level, hipStream_t s);
+hipError_t launch_write_frame(const WriteBlocksArgs &a, const WriteFrameArgs &f, hipStream_t s);
+
 }  // namespace sbam

@@ -18,7 +18,7 @@ from __future__ import annotations
 import ctypes
 import os
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -171,6 +171,20 @@ class _CrcTotals(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int64) for n in ("n_blocks", "n_bad", "first_bad", "bytes")]
 
 
+class _WriteArgs(ctypes.Structure):
+    _fields_ = [("range_lo", ctypes.c_void_p), ("range_hi", ctypes.c_void_p), ("n_ranges", ctypes.c_int64),
+                ("keep_device", ctypes.c_void_p), ("level", ctypes.c_int32), ("block_bytes", ctypes.c_int32),
+                ("with_header", ctypes.c_int32), ("with_eof", ctypes.c_int32)]
+
+
+class _WriteTotals(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ("n_records", "header_bytes", "ubytes", "n_blocks", "n_stored_blocks",
+                                              "comp_bytes")]
+
+
+WRITE_BLOCK_BYTES = 65498  # htsjdk's uncompressed bytes per BGZF block
+
+
 # sbam_load_record_fields' mask bits, the data column's dtype, its offsets column and its total
 FIELD_BITS = {"name": 1, "cigar": 2, "seq": 4, "qual": 8, "aux": 16}
 _FIELD_LAYOUT = {"name": (np.uint8, "name_off", "name_bytes"), "cigar": (np.uint32, "cigar_off", "cigar_ops"),
@@ -272,6 +286,12 @@ _SIGNATURES = {  # (restype, argtypes) of every symbol include/sbam.h declares
                                          _P(_i64)]),
     "sbam_write_bai": (ctypes.c_int, [_vp, _vp, _i64, _P(_i64)]),
     "sbam_index_long_cigar_ops": (ctypes.c_int, []),
+    "sbam_write_bam": (ctypes.c_int, [_vp, _P(_WriteArgs), _P(_WriteTotals)]),
+    "sbam_get_written": (ctypes.c_int, [_vp, _vp, _i64]),
+    "sbam_written_device": (ctypes.c_int, [_vp, _P(_vp), _P(_i64)]),
+    "sbam_get_written_blocks": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "sbam_get_written_records": (ctypes.c_int, [_vp, _vp, _vp]),
+    "sbam_test_deflate": (ctypes.c_int, [ctypes.c_int, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _P(_i64), _P(_i64)]),
     "sbam_test_exclusive_scan": (ctypes.c_int, [ctypes.c_int, _vp, _i64, _i32, _vp]),
     "sbam_test_scan_sums_int": (ctypes.c_int, [ctypes.c_int, _vp, _i64, _vp]),
     "sbam_test_chain_proof": (ctypes.c_int, [ctypes.c_int, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp,
@@ -479,6 +499,8 @@ class BamFile:
         self.header_end = None
         self.n_loaded = 0  # records of the last load_records still on the device
         self._index = None  # totals of the last build_index
+        self._written = None  # totals of the last write_bam
+        self.device = device
         if inflate:
             self.inflate()
             if contig_lengths is not None:
@@ -953,6 +975,85 @@ class BamFile:
         out = np.zeros(n.value, np.uint8)
         self._check(self.L.sbam_write_bai(self.ctx, _ptr(out), out.size, ctypes.byref(n)))
         return out.tobytes()
+
+    # ---- BAM writer
+    def _upload(self, a: np.ndarray) -> int:
+        """A device copy of a host array, allocated through the HIP runtime libsbam.so is linked to (dlsym through the
+        library's handle reaches its dependencies): the pointer is then valid in the library's kernels whichever
+        runtime torch brought along, and no torch is needed.  The caller frees it with hipFree."""
+        L = self.L
+        L.hipSetDevice.argtypes, L.hipMalloc.argtypes = [ctypes.c_int], [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+        L.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        L.hipFree.argtypes = [ctypes.c_void_p]
+        p = ctypes.c_void_p()
+        if L.hipSetDevice(self.device) or L.hipMalloc(ctypes.byref(p), max(a.nbytes, 1)):
+            raise SbamError("hipMalloc failed")
+        if a.nbytes and L.hipMemcpy(p, a.ctypes.data, a.nbytes, 1):  # hipMemcpyHostToDevice
+            L.hipFree(p)
+            raise SbamError("hipMemcpy failed")
+        return p.value
+
+    def write_bam(self, path: Optional[str] = None, ranges: Optional[Sequence[Tuple[int, int]]] = None, keep=None,
+                  level: int = 1, block_bytes: int = WRITE_BLOCK_BYTES, with_header: bool = True,
+                  with_eof: bool = True):
+        """The records of the last load_records back into BGZF bytes on the GPU (sbam_write_bam; htsjdk-rewrite,
+        HTSJDKRewrite.scala:21-91): the BAM header, then the records inside `ranges` (record-index pairs [lo, hi),
+        ascending and disjoint; None: all) whose `keep` byte is nonzero (a torch bool / uint8 tensor on this device, or
+        a numpy array, which is uploaded; None: all), cut every `block_bytes`, deflated at `level` (0 stored, 1 LZ77 +
+        fixed Huffman) and framed.  Returns the totals as a dict; the file bytes go to `path`, or with path=None into
+        the dict as "bytes"."""
+        ranges = [] if ranges is None else [(int(a), int(b)) for a, b in ranges]
+        lo = np.asarray([a for a, _ in ranges], np.int64)
+        hi = np.asarray([b for _, b in ranges], np.int64)
+        keep_ptr, staged = None, None
+        if keep is not None:
+            if int(np.prod(keep.shape)) != self.n_loaded:
+                raise ValueError(f"keep has {int(np.prod(keep.shape))} entries for {self.n_loaded} loaded records")
+            if isinstance(keep, np.ndarray):
+                staged = keep_ptr = self._upload(np.ascontiguousarray(keep).astype(np.uint8))
+            else:
+                import torch
+                if not keep.is_cuda or keep.device.index != self.device or keep.element_size() != 1:
+                    raise ValueError("keep: a bool / uint8 tensor on this BamFile's device, or a numpy array")
+                keep = keep.contiguous()
+                torch.cuda.synchronize(keep.device)
+                keep_ptr = keep.data_ptr()
+        a = _WriteArgs(_ptr(lo) if lo.size else None, _ptr(hi) if hi.size else None, lo.size,
+                       keep_ptr if self.n_loaded else None, int(level), int(block_bytes), 1 if with_header else 0,
+                       1 if with_eof else 0)
+        t = _WriteTotals()
+        try:
+            rc = self.L.sbam_write_bam(self.ctx, ctypes.byref(a), ctypes.byref(t))
+        finally:
+            if staged:
+                self.L.hipFree(ctypes.c_void_p(staged))
+        self._check(rc)
+        out = {k: int(getattr(t, k)) for k, _ in _WriteTotals._fields_}
+        self._written = out
+        data = np.zeros(out["comp_bytes"], np.uint8)
+        self._check(self.L.sbam_get_written(self.ctx, _ptr(data), data.size))
+        if path is None:
+            out = dict(out, bytes=data.tobytes())
+        else:
+            with open(path, "wb") as fh:
+                fh.write(data.tobytes())
+        return out
+
+    def written_blocks(self):
+        """(start, csize, usize) of the data blocks of the last write_bam (sbam_get_written_blocks: the new file's
+        .blocks sidecar, HTSJDKRewrite.scala:78-83)."""
+        n = self._written["n_blocks"] if self._written else 0
+        st, cs, us = np.zeros(n, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self._check(self.L.sbam_get_written_blocks(self.ctx, _ptr(st), _ptr(cs), _ptr(us)))
+        return st, cs, us
+
+    def written_records(self):
+        """(block_pos, offset) of every record the last write_bam wrote, in the new file (sbam_get_written_records:
+        its .records sidecar, HTSJDKRewrite.scala:85-90)."""
+        n = self._written["n_records"] if self._written else 0
+        bp, bo = np.zeros(n, np.int64), np.zeros(n, np.int32)
+        self._check(self.L.sbam_get_written_records(self.ctx, _ptr(bp), _ptr(bo)))
+        return bp, bo
 
     def record_spans(self, offsets: np.ndarray):
         """(ref_id, start, end) of the records at `offsets`: [getStart - 1, getEnd) as CanLoadBam.region uses it

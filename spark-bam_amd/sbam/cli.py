@@ -755,6 +755,58 @@ def index_bam_main(a) -> int:
     return 0
 
 
+# ---- htsjdk-rewrite ----------------------------------------------------------------------------------------
+def parse_read_ranges(s: str) -> List[Tuple[int, int]]:
+    """-r read-index ranges as the reference's IntRanges reads them (HTSJDKRewrite.scala:28-31): comma-separated
+    `lo-hi` (half-open) or a single index N (= [N, N+1)); plain non-negative integers, lo <= hi, ascending and
+    disjoint.  Anything else is an argument error."""
+    out = []
+    for part in s.split(","):
+        part = part.strip()
+        a, sep, b = part.partition("-")
+        if not a.isdigit() or (sep and not b.isdigit()):
+            raise argparse.ArgumentTypeError(f"bad read range {part!r}: lo-hi or a single index")
+        lo, hi = int(a), int(b) if sep else int(a) + 1
+        if hi < lo:
+            raise argparse.ArgumentTypeError(f"read range {part!r} ends before it starts")
+        if out and lo < out[-1][1]:
+            raise argparse.ArgumentTypeError(f"read range {part!r} is not behind the range before it")
+        out.append((lo, hi))
+    return out
+
+
+def _level_arg(s: str) -> int:
+    if s not in ("0", "1"):
+        raise argparse.ArgumentTypeError("level is 0 (stored) or 1 (LZ77 + fixed Huffman)")
+    return int(s)
+
+
+def _block_bytes_arg(s: str) -> int:
+    if not s.isdigit() or not 1 <= int(s) <= sbam.WRITE_BLOCK_BYTES:
+        raise argparse.ArgumentTypeError(f"block bytes are 1..{sbam.WRITE_BLOCK_BYTES}")
+    return int(s)
+
+
+def rewrite_main(a) -> int:
+    """htsjdk-rewrite (HTSJDKRewrite.scala:21-91): IN's header and its reads (those inside -r's read-index ranges) into
+    OUT through the GPU writer; -b / -i then index OUT's blocks / records into OUT.blocks / OUT.records, as
+    index-blocks and index-records do.  A range that ends past the last read is cut there, as the reference's
+    iterator simply runs out."""
+    data = open(a.bam, "rb").read()
+    with sbam.BamFile(data, path=a.bam) as f:
+        f.load_records(sbam.effective_split_size(a.max_split_size), columns=None)
+        n = f.n_loaded
+        ranges = None if a.ranges is None else [(min(lo, n), min(hi, n)) for lo, hi in a.ranges]
+        f.write_bam(a.out, ranges=ranges, level=a.level, block_bytes=a.block_bytes)
+    if a.index_blocks or a.index_records:
+        with sbam.BamFile(open(a.out, "rb").read(), path=a.out) as g:
+            if a.index_blocks:
+                write_report(index_blocks_lines(g), a.out + ".blocks")
+            if a.index_records:
+                write_report(index_records_lines(g), a.out + ".records")
+    return 0
+
+
 # ---- check-crc ---------------------------------------------------------------------------------------------
 def check_crc_lines(n_blocks: int, n_bytes: int, bad: Sequence[Tuple[int, int, int]], limit: int) -> List[str]:
     """The check-crc report: blocks and uncompressed bytes checked, then `All CRC32s match` or the mismatching blocks
@@ -822,6 +874,16 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     p.add_argument("--verify-crc", action="store_true", help="check every BGZF block's CRC32 while loading")
     p.add_argument("-m", "--max-split-size", type=parse_bytes, default=None)
     p.add_argument("bam")
+    p = sub.add_parser("htsjdk-rewrite")
+    p.add_argument("-r", "--ranges", type=parse_read_ranges, default=None,
+                   help="read-index ranges to keep, e.g. 100-1000 or 0-10,20,30-40 (half-open)")
+    p.add_argument("-b", "--index-blocks", action="store_true", help="write OUT.blocks")
+    p.add_argument("-i", "--index-records", action="store_true", help="write OUT.records")
+    p.add_argument("--level", type=_level_arg, default=1, help="0 stored, 1 LZ77 + fixed Huffman")
+    p.add_argument("--block-bytes", type=_block_bytes_arg, default=sbam.WRITE_BLOCK_BYTES)
+    p.add_argument("-m", "--max-split-size", type=parse_bytes, default=None)
+    p.add_argument("bam")
+    p.add_argument("out")
     for name in ("full-check", "check-bam", "check-blocks", "compute-splits", "count-reads", "index-blocks",
                  "index-records"):
         p = sub.add_parser(name)
@@ -853,6 +915,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         return index_bam_main(a)
     if a.cmd == "check-crc":
         return check_crc_main(a)
+    if a.cmd == "htsjdk-rewrite":
+        return rewrite_main(a)
     if getattr(a, "gpus", 1) > 1:
         if "WORLD_SIZE" not in os.environ:
             return spawn_ranks(a.gpus, sys.argv[1:] if argv is None else argv)
