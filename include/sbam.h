@@ -491,13 +491,17 @@ int sbam_index_long_cigar_ops(void);
  * selected records back to back, cut every block_bytes uncompressed bytes (htsjdk's 65498), each piece deflated and
  * framed as a BGZF block, the 28-byte EOF block last.  The uncompressed side equals the reference writer's byte for
  * byte; the compressed bytes are this library's own (level 0: stored blocks; level 1: LZ77 + the fixed Huffman code,
- * with a stored block wherever that would be smaller), deterministic for equal inputs and arguments. */
+ * with a stored block wherever that would be smaller; level 1 | SBAM_WRITE_DYNAMIC: the same LZ77 tokens, and per block
+ * the smallest of the stored form, the fixed code and a dynamic Huffman code built from the block's own counts, ties
+ * to the earlier).  Deterministic: the output is a function of the input bytes and the arguments alone, whatever the
+ * device's scheduling. */
+#define SBAM_WRITE_DYNAMIC 0x100   /* OR into level 1: per block, the smallest of stored, fixed and dynamic Huffman */
 typedef struct {
   const int64_t *range_lo;   /* host: record-index ranges [lo, hi) into the last sbam_load_records (HTSJDKRewrite.scala's */
   const int64_t *range_hi;   /* -r read-index ranges), ascending and disjoint                                         */
   int64_t n_ranges;          /* 0: every record                                                                       */
   const uint8_t *keep_device;/* optional device byte per loaded record; nonzero = keep; ANDed with the ranges         */
-  int32_t level;             /* 0 stored, 1 LZ77 + fixed Huffman                                                      */
+  int32_t level;             /* 0 stored, 1 LZ77 + fixed Huffman, 1 | SBAM_WRITE_DYNAMIC; anything else: SBAM_ERR_ARG */
   int32_t block_bytes;       /* uncompressed bytes per block, 1..65498; 0 = 65498                                     */
   int32_t with_header;       /* 1: the BAM header (stream bytes [0, header end)) goes first; needs a context that
                                 starts at file offset 0 and has read its header (sbam_header)                         */
@@ -515,10 +519,12 @@ typedef struct {
 /* Write the selected records (HTSJDKRewrite.scala:52-76: header, then every read inside the ranges).  with_header = 0
  * and with_eof = 0 exist so that the outputs of a file's shards concatenate into one valid BAM.  SBAM_ERR_STATE: no
  * sbam_load_records has run, or with_header on a context that does not start at offset 0 (or whose header has not been
- * read); SBAM_ERR_ARG: ranges out of order, overlapping or past the loaded records, level not 0 or 1, block_bytes
- * outside 0..65498.  The file bytes, the block table and the records' positions stay on the device, owned by ctx
- * (grow-only buffers: the stream at its size, the file at its stored bound of ubytes + 31 per block + 28, the deflate
- * slots at one batch of 4096 blocks), until the next sbam_write_bam, load, reset or close. */
+ * read); SBAM_ERR_ARG: ranges out of order, overlapping or past the loaded records, level not 0, 1 or
+ * 1 | SBAM_WRITE_DYNAMIC, block_bytes outside 0..65498.  The file bytes, the block table and the records' positions
+ * stay on the device, owned by ctx (grow-only buffers: the stream at its size; the file at its stored bound of
+ * ubytes + 31 per block + 28, which no form of a block exceeds; the deflate slots at one batch of at most 4096 blocks,
+ * block_bytes + 13 rounded up to 16 each; with SBAM_WRITE_DYNAMIC the token records, one per resident wavefront, at
+ * most 1024, of two bytes per block byte + 2 rounded up to 16), until the next sbam_write_bam, load, reset or close. */
 int sbam_write_bam(sbam_ctx *ctx, const sbam_write_args *args, sbam_write_totals *totals);
 /* The file bytes of the last sbam_write_bam (what HTSJDKRewrite.scala:52-76 leaves at its output path); cap smaller
  * than comp_bytes: SBAM_ERR_ARG. */
@@ -535,7 +541,10 @@ int sbam_get_written_records(sbam_ctx *ctx, int64_t *block_pos, int32_t *block_o
 /* ---- for tests: the writer's deflate and framing over arbitrary bytes (HTSJDKRewrite.scala:52-76's
  * BlockCompressedOutputStream half; no context: the call allocates its device buffers, runs on a stream of its own,
  * copies back and frees).  in[0, n) is cut every block_bytes (0 = 65498); out receives the BGZF bytes, *n_out their
- * count (cap too small: SBAM_ERR_ARG with *n_out set), *n_stored_blocks (may be NULL) the blocks in the stored form. */
+ * count (cap too small: SBAM_ERR_ARG with *n_out set), *n_stored_blocks (may be NULL) the blocks in the stored form.
+ * level as sbam_write_args.level: 0, 1 or 1 | SBAM_WRITE_DYNAMIC, else SBAM_ERR_ARG; the same bytes as sbam_write_bam
+ * gives for the same stream, a function of in, block_bytes, level and with_eof alone; the buffers sized by the same
+ * rule (the file ubytes + 31 per block + 28, slots and token records per batch). */
 int sbam_test_deflate(int device, const uint8_t *in, int64_t n, int32_t block_bytes, int32_t level, int32_t with_eof,
                       uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_stored_blocks);
 
@@ -566,8 +575,8 @@ int sbam_test_chain_proof(int device, const uint8_t *u, int64_t L, const uint64_
  * sbam_load_record_fields; "record_field_sizes": its sizes and scan), "index" (sbam_build_index, from its first pass
  * through the linear index's fill), "crc" (the block CRC32 check), "record_tags" (sbam_load_record_tags: its walk and
  * scans, "record_tag_walk", plus the gather of its byte columns, "record_tag_bytes"), "write_select", "write_gather",
- * "write_deflate", "write_frame" (sbam_write_bam's stages; deflate and frame: of its last batch of blocks). Returns -1
- * if none. */
+ * "write_deflate", "write_frame" (sbam_write_bam's stages; deflate and frame: of its last batch of blocks; the deflate
+ * stage is one launch at every level, SBAM_WRITE_DYNAMIC's tokens, codes and emit included). Returns -1 if none. */
 double sbam_last_kernel_ms(sbam_ctx *ctx, const char *kernel);
 
 #ifdef __cplusplus

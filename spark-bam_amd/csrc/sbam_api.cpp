@@ -89,7 +89,8 @@ struct TokArena {
 constexpr int64_t kWriteBatch = 4096;  // blocks deflated into the slots at a time (268 MB of stream at 65 498)
 struct Writer {
   DevBuf<uint8_t> u;      // the stream (writer_ensure_stream)
-  DevBuf<uint8_t> slots;  // one batch's fixed-Huffman payloads
+  DevBuf<uint8_t> slots;  // one batch's Huffman payloads
+  DevBuf<uint8_t> tokens; // SBAM_WRITE_DYNAMIC: one token record per workgroup of a batch's launch
   DevBuf<int32_t> cols;   // by block: payload bytes | stored | csize | usize
   DevBuf<int64_t> start;  // by block, + the end offset
   DevBuf<int64_t> tsz;    // the batch's size column, its scan's scratch and total, the stored-block counter
@@ -450,9 +451,15 @@ hipError_t ensure_index(sbam_ctx *c, size_t N, bool *grew = nullptr) {
 //   w.u      the stream, rounded up to the gather's 8-byte stores, + kWritePad
 //   w.slots  min(blocks, kWriteBatch) slots of write_slot_stride(block_bytes) bytes (the stored bound + 8, not 64 KiB),
 //            + 16: only level 1 uses them
+//   w.tokens write_token_records(batch) records of write_token_stride(block_bytes) bytes (a 16-bit entry per block
+//            byte and one for the end of block), one per workgroup of k_deflate_dynamic's grid (at most 1024), not per
+//            block: a wave is done with its record when its block is written.  Only SBAM_WRITE_DYNAMIC uses them;
+//            a batch's slots and records stay below 403 MB (268 + 134 at 65 498 bytes per block)
 //   w.cols   four int32 per block; w.start one int64 per block + 1
 //   w.tsz    kWriteBatch + 1 sizes | the scan's per-workgroup sums | its total | the stored-block counter
-//   w.file   the stored bound: ubytes + 31 per block (18 + 5 + 8) + 28; a fixed-Huffman block is never larger
+//   w.file   the stored bound: ubytes + 31 per block (18 + 5 + 8) + 28; a Huffman block is never larger
+bool write_level_ok(int32_t level) { return level == 0 || level == 1 || level == (1 | SBAM_WRITE_DYNAMIC); }
+static_assert(kWriteDynamic == SBAM_WRITE_DYNAMIC, "the flag the kernels' launcher tests is the ABI's");
 int64_t write_blocks(int64_t ubytes, int32_t block_bytes) { return (ubytes + block_bytes - 1) / block_bytes; }
 hipError_t ensure_write_stream(Writer &w, int64_t ubytes) {
   return w.u.ensure((((size_t)ubytes + 7) & ~(size_t)7) + kWritePad);
@@ -460,6 +467,8 @@ hipError_t ensure_write_stream(Writer &w, int64_t ubytes) {
 hipError_t ensure_write_blocks(Writer &w, int64_t ubytes, int32_t block_bytes, int32_t level) {
   const int64_t nb = write_blocks(ubytes, block_bytes), batch = std::min(nb, kWriteBatch);
   if (level) HIPTRY(w.slots.ensure((size_t)(batch * write_slot_stride(block_bytes) + 16)));
+  if (level & SBAM_WRITE_DYNAMIC)
+    HIPTRY(w.tokens.ensure((size_t)(write_token_records(batch) * write_token_stride(block_bytes))));
   HIPTRY(w.cols.ensure((size_t)(4 * nb)));
   HIPTRY(w.start.ensure((size_t)(nb + 1)));
   HIPTRY(w.tsz.ensure((size_t)(kWriteBatch + 1 + exclusive_scan_blocks(kWriteBatch) + 2)));
@@ -493,7 +502,8 @@ hipError_t writer_run(Writer &w, hipStream_t s, sbam_ctx *tc, int64_t ubytes, in
   int64_t base = 0, b0 = 0;
   do {
     const int64_t k = std::min(kWriteBatch, nb - b0);
-    const WriteBlocksArgs a{w.u, ubytes, block_bytes, b0, k, w.slots, write_slot_stride(block_bytes), pay, stored, w.tsz};
+    const WriteBlocksArgs a{w.u, ubytes, block_bytes, b0, k, w.slots, write_slot_stride(block_bytes), pay, stored, w.tsz,
+                            w.tokens, write_token_stride(block_bytes)};
     {
       std::unique_ptr<Timer> t(tc ? new Timer(tc, "write_deflate") : nullptr);
       HIPTRY(launch_write_deflate(a, level, s));
@@ -2127,7 +2137,9 @@ int sbam_write_bam(sbam_ctx *c, const sbam_write_args *a, sbam_write_totals *tot
   const int32_t bb = a->block_bytes == 0 ? sbam_deflate::kMaxBlockBytes : a->block_bytes;
   if (bb < 1 || bb > sbam_deflate::kMaxBlockBytes)
     return set_err(c, SBAM_ERR_ARG, "block_bytes %d outside 1..%d", (int)a->block_bytes, sbam_deflate::kMaxBlockBytes);
-  if (a->level != 0 && a->level != 1) return set_err(c, SBAM_ERR_ARG, "level %d: 0 (stored) or 1 (fixed Huffman)", (int)a->level);
+  if (!write_level_ok(a->level))
+    return set_err(c, SBAM_ERR_ARG, "level 0x%x: 0 (stored), 1 (fixed Huffman) or 1 | SBAM_WRITE_DYNAMIC = 0x%x (per block the "
+                   "smallest of stored, fixed and dynamic Huffman)", (unsigned)a->level, 1 | SBAM_WRITE_DYNAMIC);
   if (a->n_ranges < 0 || (a->n_ranges && (!a->range_lo || !a->range_hi))) return set_err(c, SBAM_ERR_ARG, "ranges missing");
   for (int64_t r = 0; r < a->n_ranges; r++) {
     const int64_t lo = a->range_lo[r], hi = a->range_hi[r];
@@ -2364,7 +2376,7 @@ int sbam_test_deflate(int device, const uint8_t *in, int64_t n, int32_t block_by
                       uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_stored_blocks) {
   if (n < 0 || cap < 0 || !n_out || (n && !in) || (cap && !out)) return SBAM_ERR_ARG;
   const int32_t bb = block_bytes == 0 ? sbam_deflate::kMaxBlockBytes : block_bytes;
-  if (bb < 1 || bb > sbam_deflate::kMaxBlockBytes || (level != 0 && level != 1)) return SBAM_ERR_ARG;
+  if (bb < 1 || bb > sbam_deflate::kMaxBlockBytes || !write_level_ok(level)) return SBAM_ERR_ARG;
   if (hipSetDevice(device) != hipSuccess) return SBAM_ERR_HIP;
   Writer w;  // (freed on every path, with this device current)
   hipStream_t s = nullptr;

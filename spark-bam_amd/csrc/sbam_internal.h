@@ -319,6 +319,8 @@ struct WriteBlocksArgs {
   int64_t slot_stride;   // write_slot_stride(block_bytes): the stored bound, not 64 KiB
   int32_t *pay, *stored; // by block: payload bytes, 1 = stored form
   int64_t *tsz;          // by k: 18 + payload + 8; scanned in place (nb + 1 entries) between deflate and frame
+  uint8_t *tokens;       // SBAM_WRITE_DYNAMIC: write_token_records(nb) records of token_stride bytes, one per workgroup
+  int64_t token_stride;  // write_token_stride(block_bytes)
 };
 struct WriteFrameArgs {
   uint8_t *file;         // 8-byte aligned
@@ -328,7 +330,10 @@ struct WriteFrameArgs {
   int32_t *csize, *usize;
   unsigned long long *n_stored;  // += stored blocks
 };
+constexpr int32_t kWriteDynamic = 0x100;  // SBAM_WRITE_DYNAMIC of sbam.h, in the level word
 int64_t write_slot_stride(int32_t block_bytes);
+int64_t write_token_stride(int32_t block_bytes);
+int64_t write_token_records(int64_t blocks);
 hipError_t launch_write_deflate(const WriteBlocksArgs &a, int32_t level, hipStream_t s);
 hipError_t launch_write_frame(const WriteBlocksArgs &a, const WriteFrameArgs &f, hipStream_t s);
 

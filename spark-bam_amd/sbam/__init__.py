@@ -30,6 +30,7 @@ ERR_HEADER_PARSE, ERR_HEADER_SEARCH, ERR_INFLATE, ERR_NO_READ_FOUND, ERR_NOT_BAM
     ERR_HALO = range(1, 10)
 ERR_RECORD = 10
 ERR_CRC = 11
+SBAM_WRITE_DYNAMIC = 0x100  # ORed into the writer's level 1: per block the smallest of stored, fixed and dynamic Huffman
 
 FLAG_NAMES = [  # check/src/main/scala/org/hammerlab/bam/check/full/error/Flags.scala:201-223
     "tooFewFixedBlockBytes", "negativeReadIdx", "tooLargeReadIdx", "negativeReadPos", "tooLargeReadPos",
@@ -995,13 +996,20 @@ class BamFile:
 
     def write_bam(self, path: Optional[str] = None, ranges: Optional[Sequence[Tuple[int, int]]] = None, keep=None,
                   level: int = 1, block_bytes: int = WRITE_BLOCK_BYTES, with_header: bool = True,
-                  with_eof: bool = True):
+                  with_eof: bool = True, huffman: str = "fixed"):
         """The records of the last load_records back into BGZF bytes on the GPU (sbam_write_bam; htsjdk-rewrite,
         HTSJDKRewrite.scala:21-91): the BAM header, then the records inside `ranges` (record-index pairs [lo, hi),
         ascending and disjoint; None: all) whose `keep` byte is nonzero (a torch bool / uint8 tensor on this device, or
         a numpy array, which is uploaded; None: all), cut every `block_bytes`, deflated at `level` (0 stored, 1 LZ77 +
-        fixed Huffman) and framed.  Returns the totals as a dict; the file bytes go to `path`, or with path=None into
-        the dict as "bytes"."""
+        Huffman codes: `huffman` = "fixed", or "dynamic" for per block the smallest of stored, fixed and dynamic,
+        level | SBAM_WRITE_DYNAMIC) and framed.  Returns the totals as a dict; the file bytes go to `path`, or with
+        path=None into the dict as "bytes"."""
+        if huffman not in ("fixed", "dynamic"):
+            raise ValueError(f"huffman is 'fixed' or 'dynamic', not {huffman!r}")
+        if huffman == "dynamic":
+            if int(level) == 0:
+                raise ValueError("huffman='dynamic' needs level 1: level 0 writes stored blocks only")
+            level = int(level) | SBAM_WRITE_DYNAMIC
         ranges = [] if ranges is None else [(int(a), int(b)) for a, b in ranges]
         lo = np.asarray([a for a, _ in ranges], np.int64)
         hi = np.asarray([b for _, b in ranges], np.int64)

@@ -777,7 +777,7 @@ def parse_read_ranges(s: str) -> List[Tuple[int, int]]:
 
 def _level_arg(s: str) -> int:
     if s not in ("0", "1"):
-        raise argparse.ArgumentTypeError("level is 0 (stored) or 1 (LZ77 + fixed Huffman)")
+        raise argparse.ArgumentTypeError("level is 0 (stored) or 1 (LZ77 + Huffman codes, fixed or --huffman dynamic)")
     return int(s)
 
 
@@ -797,7 +797,7 @@ def rewrite_main(a) -> int:
         f.load_records(sbam.effective_split_size(a.max_split_size), columns=None)
         n = f.n_loaded
         ranges = None if a.ranges is None else [(min(lo, n), min(hi, n)) for lo, hi in a.ranges]
-        f.write_bam(a.out, ranges=ranges, level=a.level, block_bytes=a.block_bytes)
+        f.write_bam(a.out, ranges=ranges, level=a.level, block_bytes=a.block_bytes, huffman=a.huffman)
     if a.index_blocks or a.index_records:
         with sbam.BamFile(open(a.out, "rb").read(), path=a.out) as g:
             if a.index_blocks:
@@ -879,7 +879,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                    help="read-index ranges to keep, e.g. 100-1000 or 0-10,20,30-40 (half-open)")
     p.add_argument("-b", "--index-blocks", action="store_true", help="write OUT.blocks")
     p.add_argument("-i", "--index-records", action="store_true", help="write OUT.records")
-    p.add_argument("--level", type=_level_arg, default=1, help="0 stored, 1 LZ77 + fixed Huffman")
+    p.add_argument("--level", type=_level_arg, default=1, help="0 stored, 1 LZ77 + Huffman codes (--huffman)")
+    p.add_argument("--huffman", choices=("fixed", "dynamic"), default="fixed",
+                   help="level 1's codes: the fixed one, or per block the smallest of stored, fixed and dynamic")
     p.add_argument("--block-bytes", type=_block_bytes_arg, default=sbam.WRITE_BLOCK_BYTES)
     p.add_argument("-m", "--max-split-size", type=parse_bytes, default=None)
     p.add_argument("bam")
@@ -916,6 +918,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     if a.cmd == "check-crc":
         return check_crc_main(a)
     if a.cmd == "htsjdk-rewrite":
+        if a.huffman == "dynamic" and a.level == 0:
+            ap.error("--huffman dynamic needs --level 1: level 0 writes stored blocks only")
         return rewrite_main(a)
     if getattr(a, "gpus", 1) > 1:
         if "WORLD_SIZE" not in os.environ:

@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """write_bench.py — the time of sbam_write_bam (gather, deflate, BGZF framing) on one MI355X.
 
-    python tools/write_bench.py [--size-gb 0.08] [--read-len 150 | --read-len 0] [--level 0 | --level 1] [--repeats 5]
+    python tools/write_bench.py [--size-gb 0.08] [--read-len 150 | --read-len 0] [--level 0 | --level 1] [--huffman fixed | dynamic]
+                                [--repeats 5]
 
 The synthetic file of tools/synth.py (bench.py's generator: --read-len 150 Illumina-like, --read-len 0 the long-read
 config) resident in HBM, inflated, its records loaded; one untimed write of every record, then --repeats writes.  The
 default size keeps the output inside one batch of deflate slots (4096 blocks), so the "write_deflate" and "write_frame"
-times cover the whole file.  Prints ONE JSON line per level (both levels without --level):
+times cover the whole file.  Prints ONE JSON line per level (both levels without --level); --huffman dynamic writes
+level 1 as 1 | SBAM_WRITE_DYNAMIC (per block the smallest of stored, fixed and dynamic Huffman; its deflate stage is one
+launch, so `deflate_ms` is its only timer) and adds `huffman` and `n_blocks_by_form` to level 1's line:
 
 * `select_ms`, `gather_ms`, `deflate_ms`, `frame_ms`: device times (sbam_last_kernel_ms), medians of the --repeats
   runs; `write_ms` their sum and `gbps` = uncompressed output bytes / write_ms;
@@ -58,6 +61,7 @@ def main() -> int:
     ap.add_argument("--size-gb", type=float, default=0.08, help="compressed GB of the input")
     ap.add_argument("--read-len", type=int, default=150, help="0 = the long-read config")
     ap.add_argument("--level", type=int, default=None, help="writer level 0 or 1 (default: both)")
+    ap.add_argument("--huffman", choices=("fixed", "dynamic"), default="fixed", help="level 1's Huffman codes")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--tile-mb", type=float, default=16.0)
     ap.add_argument("--seed", type=lambda x: int(x, 0), default=0x5EEDBA11)
@@ -77,7 +81,8 @@ def main() -> int:
         f.load_records(sbam.LOCAL_FS_BLOCK_SIZE, columns=None)
         want, z = None, None
         for level in ((0, 1) if a.level is None else (a.level,)):
-            r = f.write_bam(level=level)  # (untimed: allocates the buffers, loads the code objects)
+            huffman = a.huffman if level else "fixed"
+            r = f.write_bam(level=level, huffman=huffman)  # (untimed: allocates the buffers, loads the code objects)
             if r["n_blocks"] > 4096:
                 raise SystemExit(f"{r['n_blocks']} blocks: more than one batch, the stage times would cover the last only")
             if want is None:
@@ -85,16 +90,21 @@ def main() -> int:
                 z = zlib1(want, a.threads)
             elif gzip.decompress(r["bytes"]) != want:
                 raise SystemExit(f"parity: level {level} does not inflate to level 0's stream")
+            st, cs, _ = f.written_blocks()
+            whole = np.frombuffer(r["bytes"], np.uint8)
+            forms = np.bincount((whole[st + 18] >> 1) & 3, minlength=3).tolist()  # BTYPE of every payload
             runs = {k: [] for k in STAGES}
             for _ in range(a.repeats):
-                r = f.write_bam(level=level)
+                r = f.write_bam(level=level, huffman=huffman)
                 for k in STAGES:
                     runs[k].append(f.kernel_ms(k))
             med = {k: float(np.median(v)) for k, v in runs.items()}
             ms = sum(med.values())
             lines.append({
                 "metric": "sbam_write_bam device ms (select + gather + deflate + frame of every record)",
-                "read_len": a.read_len, "level": level, "uncompressed_gb": round(r["ubytes"] / 1e9, 4),
+                "read_len": a.read_len, "level": level, "huffman": huffman if level else None,
+                "n_blocks_by_form": {"stored": forms[0], "fixed": forms[1], "dynamic": forms[2]},
+                "uncompressed_gb": round(r["ubytes"] / 1e9, 4),
                 "n_records": r["n_records"], "n_blocks": r["n_blocks"], "n_stored_blocks": r["n_stored_blocks"],
                 "comp_bytes": r["comp_bytes"], "select_ms": round(med["write_select"], 3),
                 "gather_ms": round(med["write_gather"], 3), "deflate_ms": round(med["write_deflate"], 3),
