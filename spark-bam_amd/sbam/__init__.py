@@ -1073,14 +1073,14 @@ class BamFile:
         return r, a, b
 
     def _vpos_offset(self, v: int) -> int:
-        """Stream offset of an htsjdk virtual offset (block << 16 | offset); a block at or past the end of the
-        stream (the EOF marker) maps to the stream end."""
-        st, _, us, uo = self.blocks()
+        """Stream offset of an htsjdk virtual offset (block << 16 | offset); an address at or behind the end of the
+        last block (the EOF marker) maps to the stream end, any other address that starts no block is an error."""
+        st, cs, us, uo = self.blocks()
         b, o = v >> 16, v & 0xffff
         i = int(np.searchsorted(st, b))
         if i < st.size and int(st[i]) == b:
             return int(uo[i]) + min(o, int(us[i]))
-        if i >= st.size:
+        if i >= st.size and (st.size == 0 or b >= int(st[-1]) + int(cs[-1])):
             return self.uncompressed_size
         raise SbamError(f"no BGZF block at {b}")
 

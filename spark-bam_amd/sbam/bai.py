@@ -16,8 +16,13 @@ The htsjdk pieces restated here (htsjdk ~2.9, a third-party dependency absent fr
     chunk into the previous one when they overlap (block address, then in-block offset) or are adjacent
     (one's end == the other's start);
   * BAMFileSpan.merge over the intervals' spans: optimizeChunkList(all chunks, 0).
-Pinned by LoadBAMTest "indexed all" / "indexed disjoint regions" (chunk lists and record counts for 2.bam);
-other shapes (several references, empty bins) follow the same rules but are parity unpinned."""
+Pinned by LoadBAMTest "indexed all" / "indexed disjoint regions" (chunk lists and record counts for 2.bam).
+Other shapes are pinned to a brute-force property (tests/test_intervals_handmade.py): on coordinate-sorted files with
+several references, one of them without reads, empty bins and gaps in the linear index, the records inside the chunks
+of `file_span` whose `[start, end)` meets the loci are exactly the file's records that do, each once and in file order,
+whichever index is queried (built on the GPU, assembled on the host, the reference's own for its fixtures).  Still
+parity unpinned: whether the reference's `LociSet.intersects` keeps a mapped record of reference length 0 (the empty
+region `[pos, pos)`, kept here iff a locus has `a < pos < e`), and `MaxSplitSize`'s default."""
 from __future__ import annotations
 
 import struct

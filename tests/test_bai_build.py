@@ -360,13 +360,15 @@ def test_build_bai_fixtures(name, restated):
 @pytest.mark.gpu
 def test_load_bam_intervals_builds_its_index():
     import sbam
-    from test_intervals import CASES
+    from test_intervals import CASES, brute_offsets
+    u = Walk(fixture_bytes("2.bam")).u
     with sbam.BamFile(fixture_bytes("2.bam"), path="2.bam") as g:
         for loci, chunks, n, split, nparts in CASES:
             kw = {} if split is None else {"split_size": split}
             got_chunks, parts = g.load_bam_intervals(None, loci, **kw)
             assert [c.pos_str() for c in got_chunks] == chunks
             assert len(parts) == nparts and sum(p.size for p in parts) == n
+            assert np.concatenate(parts).tolist() == brute_offsets(u, loci), "exactly the records of the loci"
 
 
 @pytest.mark.gpu
