@@ -11,15 +11,16 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
-#include <memory>
 #include <string>
 #include <vector>
 
 #include "sbam_deflate_core.h"
 #include "sbam_internal.h"
+#include "sbam_layout.h"
 #include "sbam_tag_core.h"
 
 using namespace sbam;
+using namespace sbam_layout;
 
 namespace {
 
@@ -91,11 +92,12 @@ struct Writer {
   DevBuf<uint8_t> u;      // the stream (writer_ensure_stream)
   DevBuf<uint8_t> slots;  // one batch's Huffman payloads
   DevBuf<uint8_t> tokens; // SBAM_WRITE_DYNAMIC: one token record per workgroup of a batch's launch
-  DevBuf<int32_t> cols;   // by block: payload bytes | stored | csize | usize
+  DevBuf<uint8_t> cols;   // by block: write_cols, carved into col
   DevBuf<int64_t> start;  // by block, + the end offset
-  DevBuf<int64_t> tsz;    // the batch's size column, its scan's scratch and total, the stored-block counter
+  DevBuf<uint8_t> tsz;    // of a batch: write_sizes, carved into sz
+  WriteCols col{}; WriteSizes sz{};  // (set by ensure_write_blocks)
   DevBuf<uint8_t> file;
-  int64_t ubytes = -1, nb = 0, n_stored = 0, comp_bytes = 0;  // of the last run (ubytes -1: none)
+  int64_t ubytes = -1, nb = 0, n_stored = 0, comp_bytes = 0;  // of the last run (ubytes: set by the owner, -1: none)
   int32_t block_bytes = 0;
 };
 
@@ -200,6 +202,18 @@ struct BlockMirror {
   }
 };
 
+// The context's small device scratch: one 8-byte word per use, so that no two uses share a word by accident.
+//   scan_total, scan_overflow  scan_candidates (read back as one pair)
+//   table_first, chain_stop    sbam_scan_blocks: the lower bound, and where the chain verify stopped
+//   inflate_error              first block whose status is not 0
+//   record_count, proof_fail   sbam_record_offsets; split_counts (an int32 flag)
+//   arena_used                 TokPool::arena_used
+//   crc_bad, crc_first_bad     run_crc (written and read back as one pair)
+struct Scratch {
+  int64_t scan_total, scan_overflow, table_first, chain_stop, inflate_error, record_count, proof_fail, arena_used;
+  int64_t crc_bad, crc_first_bad;
+};
+
 }  // namespace
 
 struct sbam_ctx {
@@ -273,7 +287,7 @@ struct sbam_ctx {
   int64_t f_i0 = 0, f_n = -1;
   sbam_record_field_totals f_tot{};
   // typed tags of the last sbam_load_record_tags: the four cell columns; the byte columns' offsets, source positions
-  // and scan scratch; their bytes (ensure_tags / ensure_tag_bytes)
+  // and scan scratch; their bytes (tag_cells, tag_offs; ensure_byte_columns)
   DevBuf<uint8_t> d_tcell, d_toff, d_tdata;
   sbam_record_tags tdev{};  // device pointers (byte columns of entries without want_bytes: null)
   int64_t t_i0 = 0, t_n = -1;
@@ -287,21 +301,24 @@ struct sbam_ctx {
   DevBuf<int32_t> d_iend;
   DevBuf<uint32_t> d_ibin;
   DevBuf<int64_t> d_iheads, d_iintv;
-  DevBuf<unsigned long long> d_istat, d_irun, d_ioff;
+  DevBuf<uint8_t> d_istat;  // index_words
+  DevBuf<unsigned long long> d_irun, d_ioff;
   DevBuf<int32_t> d_irunref;
   DevBuf<uint32_t> d_irunbin;
   bool idx_built = false;
   sbam_index_totals idx_tot{};
+  IndexStats istat{};  // d_istat, carved (index_words)
   std::vector<int64_t> idx_intv;  // n_ref + 1 window offsets
-  // BAM of the last sbam_write_bam: the selection's columns (length / offset, 0-1 / ordinal, source position, scan
-  // scratch, totals), the ranges, the gather's tiles, the blocks stage, and the written records' Pos columns
-  DevBuf<int64_t> d_wsel, d_wrange, d_wtiles, d_wrpos;
+  // BAM of the last sbam_write_bam: the selection's columns (write_sel), the ranges, the gather's tiles, the blocks
+  // stage, and the written records' Pos columns
+  DevBuf<uint8_t> d_wsel;
+  DevBuf<int64_t> d_wrange, d_wtiles, d_wrpos;
   DevBuf<int32_t> d_wroff;
   Writer w;
   sbam_write_totals w_tot{};
   // small device scratch
-  DevBuf<int64_t> d_small;  // 64 int64
-  DevBuf<unsigned long long> d_counts;
+  DevBuf<int64_t> d_small;  // Scratch
+  DevBuf<uint8_t> d_counts;  // count_words
   // timing
   std::map<std::string, std::pair<hipEvent_t, hipEvent_t>> ev;
   // sbam_load's copy pieces in flight (hipEventDisableTiming events, created on first use)
@@ -311,8 +328,6 @@ struct sbam_ctx {
 };
 
 namespace {
-
-constexpr size_t kCountsWords = 21 * 19 + 21 + 21 * 128 + 19 * 19 + 4 + 19;
 
 int set_err(sbam_ctx *c, int code, const char *fmt, ...) {
   c->err.code = code;
@@ -329,10 +344,11 @@ int set_err(sbam_ctx *c, int code, const char *fmt, ...) {
     if (e_ != hipSuccess) return set_err(ctx, SBAM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
-struct Timer {  // HIP events around a launch family on the ctx stream
+struct Timer {  // HIP events around a launch family on the ctx stream (no context: nothing)
   sbam_ctx *c;
-  std::pair<hipEvent_t, hipEvent_t> *e;
+  std::pair<hipEvent_t, hipEvent_t> *e = nullptr;
   Timer(sbam_ctx *c_, const char *name) : c(c_) {
+    if (!c) return;
     auto it = c->ev.find(name);
     if (it == c->ev.end()) {
       std::pair<hipEvent_t, hipEvent_t> p;
@@ -343,8 +359,23 @@ struct Timer {  // HIP events around a launch family on the ctx stream
     e = &it->second;
     (void)hipEventRecord(e->first, c->stream);
   }
-  ~Timer() { (void)hipEventRecord(e->second, c->stream); }
+  ~Timer() { if (c) (void)hipEventRecord(e->second, c->stream); }
 };
+
+// a word of the small scratch, by name
+#define SMALL(c, word) ((c)->d_small.get() + offsetof(Scratch, word) / 8)
+#define USMALL(c, word) reinterpret_cast<unsigned long long *>(SMALL(c, word))
+
+// An arena by its layout (sbam_layout.h): the null pass sizes the buffer, the second pass carves it.
+template <class F>
+hipError_t carve(DevBuf<uint8_t> &buf, bool *grew, F &&layout) {
+  Carve size(nullptr);
+  layout(size);
+  HIPTRY(buf.ensure(size.bytes(), grew));
+  Carve k(buf.get());
+  layout(k);
+  return hipSuccess;
+}
 
 StreamView view(sbam_ctx *c) {
   return StreamView{c->d_u, c->L, c->d_lens, c->nref, (c->base + c->D >= c->file_size) ? 1 : 0};
@@ -361,19 +392,24 @@ void set_bitmap(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, bool list_form) 
 }
 void drop_bitmap(sbam_ctx *c) { c->bm_valid = c->bm_list = c->rp_fetch = false; }
 
-// The stages a context can hold: candidates, block table, stream (with its bitmap), records (with their fields).
+// The stages a context can hold, in the order they are made: candidates -> table -> stream -> {crc, bitmap, records},
+// records -> {fields, tags, index, written}.  A producer drops its own stage, and with it everything made from it,
+// before it touches a buffer (drop_from), and sets its stage's validity field as its last step; nothing else clears one.
+enum Stage { kCandidates, kTable, kStream, kCrc, kBitmap, kRecords, kFields, kTags, kIndex, kWritten };
 bool any_stage_ran(const sbam_ctx *c) { return c->ncand >= 0 || c->blk.n >= 0 || c->L >= 0 || c->n_loaded >= 0; }
-hipError_t drop_stages(sbam_ctx *c) {
-  c->ncand = -1;
-  const hipError_t e = c->blk.invalidate();
-  c->L = -1;
-  c->inflate_slow = -1;
-  c->crc_b0 = c->crc_b1 = -1;
-  drop_bitmap(c);
-  c->n_loaded = -1;
-  c->f_n = c->t_n = -1;
-  c->loaded_all = c->idx_built = false;
-  c->w.ubytes = -1;
+// Returns the table mirror's invalidate() (a wait for a copy in flight), hipSuccess for every other stage.
+hipError_t drop_from(sbam_ctx *c, Stage from) {
+  const bool stream = from <= kStream, records = stream || from == kRecords;
+  if (from == kCandidates) c->ncand = -1;
+  const hipError_t e = from <= kTable ? c->blk.invalidate() : hipSuccess;
+  if (stream) c->L = c->inflate_slow = -1;
+  if (stream || from == kCrc) c->crc_b0 = c->crc_b1 = -1;
+  if (stream || from == kBitmap) drop_bitmap(c);
+  if (records) c->n_loaded = -1, c->loaded_all = false;
+  if (records || from == kFields) c->f_n = -1;
+  if (records || from == kTags) c->t_n = -1;
+  if (records || from == kIndex) c->idx_built = false;
+  if (records || from == kWritten) c->w.ubytes = -1;
   return e;
 }
 
@@ -425,19 +461,18 @@ hipError_t ensure_chain_list(sbam_ctx *c, size_t n, bool *grew = nullptr) {
   HIPTRY(c->d_pok.ensure(n, grew));
   return c->d_nfb.ensure(3);
 }
-// loadReads' N records: the offset column, and an int64 column and ten int32 ones (each 256-B aligned) in one
-// arena, carved into *cols
+// loadReads' N records: the offset column, and record_cols in one arena, carved into *cols
 hipError_t ensure_record_columns(sbam_ctx *c, size_t N, bool *grew = nullptr, RecordColumnsDev *cols = nullptr) {
   HIPTRY(c->d_roff.ensure(N, grew));
-  const size_t stride = (std::max<size_t>(N, 1) * 8 + 255) & ~(size_t)255;
-  const size_t stride4 = (std::max<size_t>(N, 1) * 4 + 255) & ~(size_t)255;
-  HIPTRY(c->d_rcols.ensure(stride + 10 * stride4, grew));
-  if (!cols) return hipSuccess;
-  uint8_t *p = c->d_rcols;
-  auto q = [&](int j) { return reinterpret_cast<int32_t *>(p + stride + j * stride4); };
-  auto qu = [&](int j) { return reinterpret_cast<uint32_t *>(q(j)); };
-  *cols = RecordColumnsDev{reinterpret_cast<int64_t *>(p), q(0), q(1), q(2), q(3), qu(4), qu(5), q(6), q(7), q(8), q(9)};
-  return hipSuccess;
+  RecordColumnsDev r;
+  return carve(c->d_rcols, grew, [&](Carve &k) { (cols ? *cols : r) = record_cols<RecordColumnsDev>(k, N); });
+}
+// byte columns of bytes[i] bytes (< 0: none) with their gather tiles (byte_col): the fields' data, the tags' bytes
+hipError_t ensure_byte_columns(DevBuf<uint8_t> &buf, int ncol, const int64_t *bytes, ByteCol *o, bool *grew = nullptr) {
+  return carve(buf, grew, [&](Carve &k) {
+    for (int i = 0; i < ncol; i++)
+      if (bytes[i] >= 0) o[i] = byte_col(k, (size_t)bytes[i], (size_t)field_gather_tiles(bytes[i]));
+  });
 }
 
 // the index's per-record scratch and run heads for N records
@@ -455,8 +490,8 @@ hipError_t ensure_index(sbam_ctx *c, size_t N, bool *grew = nullptr) {
 //            byte and one for the end of block), one per workgroup of k_deflate_dynamic's grid (at most 1024), not per
 //            block: a wave is done with its record when its block is written.  Only SBAM_WRITE_DYNAMIC uses them;
 //            a batch's slots and records stay below 403 MB (268 + 134 at 65 498 bytes per block)
-//   w.cols   four int32 per block; w.start one int64 per block + 1
-//   w.tsz    kWriteBatch + 1 sizes | the scan's per-workgroup sums | its total | the stored-block counter
+//   w.cols   write_cols; w.start one int64 per block + 1
+//   w.tsz    write_sizes of kWriteBatch blocks
 //   w.file   the stored bound: ubytes + 31 per block (18 + 5 + 8) + 28; a Huffman block is never larger
 bool write_level_ok(int32_t level) { return level == 0 || level == 1 || level == (1 | SBAM_WRITE_DYNAMIC); }
 static_assert(kWriteDynamic == SBAM_WRITE_DYNAMIC, "the flag the kernels' launcher tests is the ABI's");
@@ -469,107 +504,48 @@ hipError_t ensure_write_blocks(Writer &w, int64_t ubytes, int32_t block_bytes, i
   if (level) HIPTRY(w.slots.ensure((size_t)(batch * write_slot_stride(block_bytes) + 16)));
   if (level & SBAM_WRITE_DYNAMIC)
     HIPTRY(w.tokens.ensure((size_t)(write_token_records(batch) * write_token_stride(block_bytes))));
-  HIPTRY(w.cols.ensure((size_t)(4 * nb)));
+  HIPTRY(carve(w.cols, nullptr, [&](Carve &k) { w.col = write_cols(k, (size_t)nb); }));
   HIPTRY(w.start.ensure((size_t)(nb + 1)));
-  HIPTRY(w.tsz.ensure((size_t)(kWriteBatch + 1 + exclusive_scan_blocks(kWriteBatch) + 2)));
+  HIPTRY(carve(w.tsz, nullptr,
+               [&](Carve &k) { w.sz = write_sizes(k, kWriteBatch, exclusive_scan_blocks(kWriteBatch)); }));
   return w.file.ensure((size_t)(ubytes + 31 * nb + 28));
-}
-// the selection over N loaded records: two columns of N + 2, the sources (N + 1), the scan's sums, two totals
-struct WriteSelLayout {
-  size_t stride, src, bsum, tot, words;
-};
-WriteSelLayout write_sel_layout(size_t N) {
-  WriteSelLayout l;
-  l.stride = N + 2;
-  l.src = 2 * l.stride;
-  l.bsum = l.src + N + 1;
-  l.tot = l.bsum + 2 * (size_t)exclusive_scan_blocks((int64_t)N + 1);
-  l.words = l.tot + 2;
-  return l;
 }
 
 // Deflate and frame w.u[0, ubytes) into w.file, a batch of blocks at a time; the host reads each batch's size (8 bytes)
 // to place the next.  tc: the context whose timers record the stages (nullptr: none).
 hipError_t writer_run(Writer &w, hipStream_t s, sbam_ctx *tc, int64_t ubytes, int32_t block_bytes, int32_t level,
                       bool with_eof) {
-  w.ubytes = -1;
   HIPTRY(ensure_write_blocks(w, ubytes, block_bytes, level));
   const int64_t nb = write_blocks(ubytes, block_bytes);
-  int32_t *pay = w.cols, *stored = pay + nb, *csize = stored + nb, *usize = csize + nb;
-  int64_t *bsum = w.tsz + kWriteBatch + 1, *tot = bsum + exclusive_scan_blocks(kWriteBatch);
-  unsigned long long *n_stored = reinterpret_cast<unsigned long long *>(tot + 1);
-  HIPTRY(hipMemsetAsync(n_stored, 0, 8, s));
+  HIPTRY(hipMemsetAsync(w.sz.n_stored, 0, 8, s));
   int64_t base = 0, b0 = 0;
   do {
     const int64_t k = std::min(kWriteBatch, nb - b0);
-    const WriteBlocksArgs a{w.u, ubytes, block_bytes, b0, k, w.slots, write_slot_stride(block_bytes), pay, stored, w.tsz,
-                            w.tokens, write_token_stride(block_bytes)};
+    const WriteBlocksArgs a{w.u, ubytes, block_bytes, b0, k, w.slots, write_slot_stride(block_bytes), w.col.pay, w.col.stored,
+                            w.sz.tsz, w.tokens, write_token_stride(block_bytes)};
     {
-      std::unique_ptr<Timer> t(tc ? new Timer(tc, "write_deflate") : nullptr);
+      Timer t(tc, "write_deflate");
       HIPTRY(launch_write_deflate(a, level, s));
     }
     {
-      std::unique_ptr<Timer> t(tc ? new Timer(tc, "write_frame") : nullptr);
-      HIPTRY(launch_exclusive_scan(w.tsz, k + 1, k, 1, bsum, tot, s));
-      const WriteFrameArgs f{w.file, base, (with_eof && b0 + k >= nb) ? 1 : 0, w.start, csize, usize, n_stored};
+      Timer t(tc, "write_frame");
+      HIPTRY(launch_exclusive_scan(w.sz.tsz, k + 1, k, 1, w.sz.bsum, w.sz.tot, s));
+      const WriteFrameArgs f{w.file, base, (with_eof && b0 + k >= nb) ? 1 : 0, w.start, w.col.csize, w.col.usize, w.sz.n_stored};
       HIPTRY(launch_write_frame(a, f, s));
     }
     int64_t bytes = 0;
-    HIPTRY(hipMemcpyAsync(&bytes, tot, 8, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(&bytes, w.sz.tot, 8, hipMemcpyDeviceToHost, s));
     HIPTRY(hipStreamSynchronize(s));
     base += bytes;
     b0 += k;
   } while (b0 < nb);
   unsigned long long ns = 0;
-  HIPTRY(hipMemcpy(&ns, n_stored, 8, hipMemcpyDeviceToHost));
-  w.ubytes = ubytes;
+  HIPTRY(hipMemcpy(&ns, w.sz.n_stored, 8, hipMemcpyDeviceToHost));
   w.nb = nb;
   w.n_stored = (int64_t)ns;
   w.comp_bytes = base + (with_eof ? 28 : 0);
   w.block_bytes = block_bytes;
   return hipSuccess;
-}
-
-// Typed tags of n records, nq query entries, nb of them with a byte column.  Every piece is 256-B aligned.
-//   d_tcell  type | sub | rel | value, nq * n entries each
-//   d_toff   nb offset columns of n + 1 int64 | nb source-position columns of n | the scans' per-workgroup sums |
-//            first bad record, 32 byte totals, kTagPresentSlots x 32 present counters
-constexpr size_t kTagSmallWords = 1 + SBAM_MAX_TAGS + (size_t)kTagPresentSlots * SBAM_MAX_TAGS;
-struct TagLayout {
-  size_t sub, rel, value, cell_bytes;       // offsets into d_tcell, and its size
-  size_t ostride, src, bsum, small, off_bytes;  // (ostride: bytes per offset column) offsets into d_toff, and its size
-};
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-TagLayout tag_layout(size_t n, size_t nq, size_t nb) {
-  TagLayout t;
-  const size_t cells = nq * n;
-  t.sub = up256(cells);
-  t.rel = t.sub + up256(cells);
-  t.value = t.rel + up256(cells * 4);
-  t.cell_bytes = t.value + up256(cells * 8);
-  t.ostride = up256((n + 1) * 8);
-  t.src = nb * t.ostride;
-  t.bsum = t.src + nb * up256(n * 8);
-  t.small = t.bsum + up256(nb * (size_t)exclusive_scan_blocks((int64_t)n) * 8);
-  t.off_bytes = t.small + up256(kTagSmallWords * 8);
-  return t;
-}
-hipError_t ensure_tags(sbam_ctx *c, const TagLayout &t, bool *grew = nullptr) {
-  HIPTRY(c->d_tcell.ensure(t.cell_bytes, grew));
-  return c->d_toff.ensure(t.off_bytes, grew);
-}
-// the byte columns (each padded to the gather's 8-byte stores) with the gather's per-tile record ranges behind each;
-// at[b], tiles_at[b]: column b's offsets into d_tdata
-hipError_t ensure_tag_bytes(sbam_ctx *c, const int64_t *bytes, int nb, size_t *at, size_t *tiles_at,
-                            bool *grew = nullptr) {
-  size_t need = 0;
-  for (int b = 0; b < nb; b++) {
-    at[b] = need;
-    need += up256((size_t)bytes[b] + 8);
-    tiles_at[b] = need;
-    need += up256((size_t)field_gather_tiles(bytes[b]) * 16);
-  }
-  return c->d_tdata.ensure(need, grew);
 }
 
 // Header.make details at relative offset q (for HeaderParseException).
@@ -597,6 +573,14 @@ int no_read_found(sbam_ctx *c, int64_t start, int32_t max_read_size) {
   c->err.expected = max_read_size;
   return set_err(c, SBAM_ERR_NO_READ_FOUND, "Failed to find a valid read-start in %d attempts in %s from %lld",
                  max_read_size, c->path.c_str(), (long long)start);
+}
+
+// SBAM_ERR_RECORD for loaded record i, with its stream offset (the fields' and the tags' first bad record)
+int bad_record(sbam_ctx *c, int64_t i, const char *what) {
+  int64_t x = -1;
+  HIPCHK(c, hipMemcpy(&x, c->d_roff + i, 8, hipMemcpyDeviceToHost));
+  c->err.position = x;
+  return set_err(c, SBAM_ERR_RECORD, "record %lld at %lld: %s", (long long)i, (long long)x, what);
 }
 
 // a scanned block table, with its host copy in c->blk's vectors
@@ -663,8 +647,8 @@ int sbam_open(int device, const uint8_t *data, int64_t len, int64_t base_offset,
   HIPCHK(c, c->d_comp.ensure((size_t)len + kCompPad));
   HIPCHK(c, hipMemsetAsync(c->d_comp + len, 0, kCompPad, c->stream));
   if (len) HIPCHK(c, hipMemcpyAsync(c->d_comp, data, (size_t)len, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, c->d_small.ensure(64));
-  HIPCHK(c, c->d_counts.ensure(kCountsWords));
+  HIPCHK(c, c->d_small.ensure(sizeof(Scratch) / 8));
+  HIPCHK(c, carve(c->d_counts, nullptr, count_words<CountsDev>));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SBAM_OK;
 }
@@ -756,7 +740,7 @@ int sbam_reserve(sbam_ctx *c, int64_t comp_bytes, int64_t n_blocks, int64_t ubyt
 
 int sbam_reset(sbam_ctx *c) {
   if (!c) return SBAM_ERR_ARG;
-  const hipError_t e = drop_stages(c);
+  const hipError_t e = drop_from(c, kCandidates);
   c->err = sbam_error{};
   HIPCHK(c, e);
   return SBAM_OK;
@@ -781,11 +765,11 @@ static int scan_candidates(sbam_ctx *c) {
   Timer t(c, "scan");
   const int64_t nchunks = scan_chunks(c->D);
   HIPCHK(c, ensure_scan(c, c->D));
-  // one pass into per-chunk slots (+ counts, exact even past the slots); d_small[0] = total, [1] = overflow
-  HIPCHK(c, launch_scan_slots(c->d_comp, c->D, c->d_cc, nchunks, c->d_slots, c->d_small + 1, c->stream));
-  HIPCHK(c, launch_scan_sums(c->d_cc, c->d_coff, nchunks, 1, c->d_small, c->stream));
+  // one pass into per-chunk slots (+ counts, exact even past the slots)
+  HIPCHK(c, launch_scan_slots(c->d_comp, c->D, c->d_cc, nchunks, c->d_slots, SMALL(c, scan_overflow), c->stream));
+  HIPCHK(c, launch_scan_sums(c->d_cc, c->d_coff, nchunks, 1, SMALL(c, scan_total), c->stream));
   int64_t tot_ovf[2] = {0, 0};
-  HIPCHK(c, hipMemcpyAsync(tot_ovf, c->d_small, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(tot_ovf, SMALL(c, scan_total), 2 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const int64_t total = tot_ovf[0];
   HIPCHK(c, c->d_cand.ensure(total));
@@ -832,7 +816,7 @@ int sbam_find_block_starts(sbam_ctx *c, const int64_t *starts, int64_t n, int32_
 int sbam_scan_blocks(sbam_ctx *c, int64_t *n_blocks) {
   if (!c) return SBAM_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, c->blk.invalidate());  // (no table until this scan has built one)
+  HIPCHK(c, drop_from(c, kTable));  // (no table, and nothing made from one, until this scan has built one)
   int rc = scan_candidates(c);
   if (rc) return rc;
   int64_t start_rel = 0;
@@ -844,8 +828,8 @@ int sbam_scan_blocks(sbam_ctx *c, int64_t *n_blocks) {
   }
   Timer t(c, "chain");
   int64_t first = 0;
-  HIPCHK(c, launch_lower_bound(c->d_cand, c->ncand, start_rel, c->d_small, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&first, c->d_small, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, launch_lower_bound(c->d_cand, c->ncand, start_rel, SMALL(c, table_first), c->stream));
+  HIPCHK(c, hipMemcpyAsync(&first, SMALL(c, table_first), sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   int64_t nb = 0;
   bool fast = true;
@@ -856,10 +840,10 @@ int sbam_scan_blocks(sbam_ctx *c, int64_t *n_blocks) {
     if (first < c->ncand) HIPCHK(c, hipMemcpy(&c0, c->d_cand + first, sizeof(Candidate), hipMemcpyDeviceToHost));
     if (first >= c->ncand || c0.pos != start_rel) return header_parse_error(c, start_rel);
     const unsigned long long none = ~0ull;
-    HIPCHK(c, hipMemcpyAsync(c->d_small + 1, &none, sizeof(none), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_chain_verify(c->d_cand, c->ncand, first, c->D, c->d_small + 1, c->stream));
+    HIPCHK(c, hipMemcpyAsync(SMALL(c, chain_stop), &none, sizeof(none), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_chain_verify(c->d_cand, c->ncand, first, c->D, SMALL(c, chain_stop), c->stream));
     unsigned long long stop = 0;
-    HIPCHK(c, hipMemcpyAsync(&stop, c->d_small + 1, sizeof(stop), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&stop, SMALL(c, chain_stop), sizeof(stop), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int64_t si = (int64_t)(stop >> 2);
     const int code = (int)(stop & 3);
@@ -930,13 +914,13 @@ int sbam_inflate(sbam_ctx *c, int64_t *usz) {
   int64_t L = 0;
   HIPCHK(c, c->blk.total(&L));  // (the table's host copy is picked up below, while the decoder runs)
   const int64_t nb = c->blk.n;
-  c->crc_b0 = c->crc_b1 = -1;  // (a check's results describe the stream this call replaces)
+  HIPCHK(c, drop_from(c, kStream));  // (no stream, and nothing made from one, until this call has decoded one)
   HIPCHK(c, ensure_inflate(c, L, nb));
   HIPCHK(c, hipMemsetAsync(c->d_u + L, 0, kStreamPad, c->stream));
   int32_t *d_status = c->d_status, *d_found = c->d_found;
   const unsigned long long none = ~0ull;
   BlockTable bt{c->d_bstart, c->d_bh, c->d_bc, c->d_bu, c->d_buoff, nb};
-  unsigned long long *d_used = reinterpret_cast<unsigned long long *>(c->d_small + 16);
+  unsigned long long *d_used = USMALL(c, arena_used), *d_ferr = USMALL(c, inflate_error);
   unsigned long long ferr = 0;
   unsigned int cnt3[3] = {0, 0, 0};  // slow-path blocks, -, blocks the resolver handed back
   for (;;) {
@@ -956,17 +940,17 @@ int sbam_inflate(sbam_ctx *c, int64_t *usz) {
     // the table's host copy, while the kernels run (before the copies of the results below: copies into pageable
     // memory wait for the stream)
     HIPCHK(c, c->blk.get());
-    HIPCHK(c, hipMemcpyAsync(c->d_small + 2, &none, 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_first_error(d_status, nb, reinterpret_cast<unsigned long long *>(c->d_small + 2), c->stream));
-    HIPCHK(c, hipMemcpyAsync(&ferr, c->d_small + 2, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_ferr, &none, 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_first_error(d_status, nb, d_ferr, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&ferr, d_ferr, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(cnt3, c->d_icnt, 12, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (cnt3[2] > 0) {  // a distance past its block's start ("invalid distance too far back"): the exact decoder
       HIPCHK(c, launch_inflate_redo(c->d_comp, c->D, bt, tp, c->d_slow, c->d_icnt, d_status, d_found, c->stream));
       HIPCHK(c, launch_inflate_resolve(bt, c->d_u, tp, d_found, c->d_slow, cnt3[2], nullptr, nullptr, c->stream));
-      HIPCHK(c, hipMemcpyAsync(c->d_small + 2, &none, 8, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, launch_first_error(d_status, nb, reinterpret_cast<unsigned long long *>(c->d_small + 2), c->stream));
-      HIPCHK(c, hipMemcpyAsync(&ferr, c->d_small + 2, 8, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(d_ferr, &none, 8, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, launch_first_error(d_status, nb, d_ferr, c->stream));
+      HIPCHK(c, hipMemcpyAsync(&ferr, d_ferr, 8, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     if (ferr == ~0ull) break;
@@ -979,7 +963,6 @@ int sbam_inflate(sbam_ctx *c, int64_t *usz) {
     if (log_grow()) std::fprintf(stderr, "[sbam] token arena %zu -> %llu bytes\n", c->arena.usable(), used);
     HIPCHK(c, c->arena.ensure((size_t)used + (used >> 3)));
   }
-  c->inflate_slow = cnt3[0] + cnt3[2];
   if (ferr != ~0ull) {
     int32_t found = 0;
     HIPCHK(c, hipMemcpy(&found, d_found + ferr, 4, hipMemcpyDeviceToHost));
@@ -1000,15 +983,14 @@ int sbam_inflate(sbam_ctx *c, int64_t *usz) {
       c->err.position = c->base + c->blk.start[b];
       c->err.expected = want;
       c->err.actual = got;
-      c->L = -1;
       return set_err(c, SBAM_ERR_CRC, "CRC32 mismatch in block at %lld: footer %08x, computed %08x",
                      (long long)c->err.position, want, got);
     }
     c->crc_b0 = 0;
     c->crc_b1 = nb;
   }
+  c->inflate_slow = cnt3[0] + cnt3[2];
   c->L = L;
-  drop_bitmap(c);
   if (usz) *usz = L;
   return SBAM_OK;
 }
@@ -1019,7 +1001,7 @@ int sbam_inflate(sbam_ctx *c, int64_t *usz) {
 static int run_crc(sbam_ctx *c, int64_t L, int64_t b0, int64_t b1, unsigned long long bad[2]) {
   const int64_t nb = c->blk.n;
   HIPCHK(c, ensure_crc(c, nb));
-  unsigned long long *d_bad = reinterpret_cast<unsigned long long *>(c->d_small + 24);
+  unsigned long long *d_bad = USMALL(c, crc_bad);  // (and crc_first_bad behind it)
   bad[0] = 0;
   bad[1] = ~0ull;
   HIPCHK(c, hipMemcpyAsync(d_bad, bad, 16, hipMemcpyHostToDevice, c->stream));
@@ -1051,6 +1033,7 @@ int sbam_check_crc(sbam_ctx *c, int64_t b0, int64_t b1, sbam_crc_totals *totals)
     return set_err(c, SBAM_ERR_ARG, "blocks [%lld, %lld) outside the table of %lld", (long long)b0, (long long)b1,
                    (long long)nb);
   HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, drop_from(c, kCrc));
   unsigned long long bad[2];
   rc = run_crc(c, c->L, b0, b1, bad);
   if (rc) return rc;
@@ -1198,7 +1181,7 @@ int sbam_check_eager(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, uint64_t *b
   int rc = check_range_args(c, x0, x1, R);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  drop_bitmap(c);
+  HIPCHK(c, drop_from(c, kBitmap));
   HIPCHK(c, ensure_bitmap(c, x0, x1));
   bool list_form = false;
   {
@@ -1223,7 +1206,7 @@ int sbam_check_full_words(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, uint32
   int rc = check_range_args(c, x0, x1, R);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  drop_bitmap(c);
+  HIPCHK(c, drop_from(c, kBitmap));
   DevBuf<uint32_t> d_w;  // (per-call: one word per position)
   HIPCHK(c, d_w.ensure(x1 - x0));
   HIPCHK(c, ensure_bitmap(c, x0, x1));
@@ -1268,17 +1251,13 @@ int sbam_check_full_counts(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, int32
   int rc = check_range_args(c, x0, x1, R);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  drop_bitmap(c);
+  HIPCHK(c, drop_from(c, kBitmap));
   HIPCHK(c, ensure_check(c, x0, x1));
-  HIPCHK(c, hipMemsetAsync(c->d_counts, 0, kCountsWords * 8, c->stream));
-  CountsDev cd;
-  cd.counts = c->d_counts;
-  cd.positions = cd.counts + 21 * 19;
-  cd.rbe = cd.positions + 21;
-  cd.pair = cd.rbe + 21 * 128;
-  cd.scalars = cd.pair + 19 * 19;
-  cd.totals = cd.scalars + 4;
+  Carve k(c->d_counts.get());
+  CountsDev cd = count_words<CountsDev>(k);
   cd.tile_pass0 = c->d_tcnt;
+  const size_t words = cd.totals + SBAM_NUM_FLAGS - cd.counts;  // (one run)
+  HIPCHK(c, hipMemsetAsync(cd.counts, 0, words * 8, c->stream));
   bool tiles = false, list_form = false;
   {
     Timer t(c, "check_full");
@@ -1289,32 +1268,26 @@ int sbam_check_full_counts(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, int32
     Timer t1(c, "check_chains");
     HIPCHK(c, run_chains(c, x0, x1, R, by_key, cd, &list_form, tiles ? c->d_tcnt.get() : nullptr));
   }
-  std::vector<unsigned long long> h(kCountsWords);
-  HIPCHK(c, hipMemcpyAsync(h.data(), c->d_counts, kCountsWords * 8, hipMemcpyDeviceToHost, c->stream));
+  std::vector<unsigned long long> hw(words);
+  HIPCHK(c, hipMemcpyAsync(hw.data(), cd.counts, words * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (bitmap) {
     int rc2 = copy_bitmap_out(c, x0, x1, bitmap);
     if (rc2) return rc2;
   }
+  // the host's copy has the device's layout
   memset(out, 0, sizeof(*out));
-  const unsigned long long *p = h.data();
-  for (int k = 0; k < 21; k++)
-    for (int f = 0; f < 19; f++) out->counts[k][f] = (int64_t)p[k * 19 + f];
-  p += 21 * 19;
-  for (int k = 0; k < 21; k++) out->positions[k] = (int64_t)p[k];
-  p += 21;
-  for (int k = 0; k < 21; k++)
-    for (int r = 0; r < 128; r++) out->reads_before_error[k][r] = (int64_t)p[k * 128 + r];
-  p += 21 * 128;
-  for (int i = 0; i < 19; i++)
-    for (int j = 0; j < 19; j++) out->pair_hist[i][j] = (int64_t)p[i * 19 + j];
-  p += 19 * 19;
+  Carve hk(hw.data());
+  const CountsDev h = count_words<CountsDev>(hk);
+  std::memcpy(out->counts, h.counts, sizeof(out->counts));
+  std::memcpy(out->positions, h.positions, sizeof(out->positions));
+  std::memcpy(out->reads_before_error, h.rbe, sizeof(out->reads_before_error));
+  std::memcpy(out->pair_hist, h.pair, sizeof(out->pair_hist));
+  std::memcpy(out->totals, h.totals, sizeof(out->totals));
   out->n_positions = x1 - x0;
-  out->n_success = (int64_t)p[1];
-  out->n_too_few_fixed = (int64_t)p[2];
-  out->n_halo = (int64_t)p[3];
-  p += 4;
-  for (int f = 0; f < 19; f++) out->totals[f] = (int64_t)p[f];
+  out->n_success = (int64_t)h.scalars[1];
+  out->n_too_few_fixed = (int64_t)h.scalars[2];
+  out->n_halo = (int64_t)h.scalars[3];
   set_bitmap(c, x0, x1, R, list_form);
   if (out->n_halo) {
     c->err.actual = out->n_halo;
@@ -1454,7 +1427,7 @@ static int split_counts(sbam_ctx *c, bool try_bitmap, const std::vector<int64_t>
   const int64_t X1 = *std::max_element(xe.begin(), xe.end());
   Timer t(c, "records");
   if (try_bitmap && c->bm_valid && X0 >= c->bm_x0 && X1 <= c->bm_x1) {
-    int32_t *d_fail = reinterpret_cast<int32_t *>(c->d_small + 8);
+    int32_t *d_fail = reinterpret_cast<int32_t *>(SMALL(c, proof_fail));
     const int64_t xa = c->bm_x0 & ~(int64_t)63;
     HIPCHK(c, hipMemsetAsync(d_fail, 0, 4, c->stream));
     // SBAM_FORCE_PROOF=1 (measurement): run the proof even when the list pass found every link, as a bitmap with one
@@ -1536,9 +1509,9 @@ int sbam_record_offsets(sbam_ctx *c, int64_t x0, int64_t x_end, int64_t *offsets
   HIPCHK(c, hipSetDevice(c->device));
   DevBuf<int64_t> d_o;  // (per-call)
   HIPCHK(c, d_o.ensure(cap));
-  HIPCHK(c, launch_record_offsets(view(c), x0, std::min(x_end, c->L), d_o, cap, c->d_small + 4, c->stream));
+  HIPCHK(c, launch_record_offsets(view(c), x0, std::min(x_end, c->L), d_o, cap, SMALL(c, record_count), c->stream));
   int64_t n = 0;
-  HIPCHK(c, hipMemcpyAsync(&n, c->d_small + 4, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&n, SMALL(c, record_count), 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (n < 0) n = -(n + 3);
   if (offsets && n) HIPCHK(c, hipMemcpy(offsets, d_o, std::min(n, cap) * 8, hipMemcpyDeviceToHost));
@@ -1572,9 +1545,7 @@ int sbam_load_records(sbam_ctx *c, const sbam_split_args *a, int64_t first, int6
   int rc = ensure_stream(c);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  c->n_loaded = -1;
-  c->f_n = c->t_n = -1;
-  c->loaded_all = c->idx_built = false;
+  HIPCHK(c, drop_from(c, kRecords));
   std::vector<int64_t> xs, xe, cnt;
   rc = split_starts(c, a, first, count, xs, xe);
   if (rc) return rc;
@@ -1671,7 +1642,7 @@ int sbam_load_record_fields(sbam_ctx *c, int64_t i0, int64_t n, uint32_t fields,
                    (long long)c->n_loaded);
   if (fields == 0 || (fields & ~kAll)) return set_err(c, SBAM_ERR_ARG, "field mask 0x%x", (unsigned)fields);
   HIPCHK(c, hipSetDevice(c->device));
-  c->f_n = -1;
+  HIPCHK(c, drop_from(c, kFields));
   c->fdev = sbam_record_fields{};
   c->f_tot = sbam_record_field_totals{};
   if (totals) *totals = c->f_tot;
@@ -1680,62 +1651,42 @@ int sbam_load_record_fields(sbam_ctx *c, int64_t i0, int64_t n, uint32_t fields,
     c->f_n = 0;
     return SBAM_OK;
   }
-  // offsets arena: four int64 columns of n + 1, the scan's per-workgroup sums, first bad record + four totals
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t ostride = up((size_t)(n + 1) * 8), nblk = (size_t)field_size_blocks(n);
-  HIPCHK(c, c->d_foff.ensure(4 * ostride + up(4 * nblk * 8) + 256));
-  int64_t *off[4];
-  for (int f = 0; f < 4; f++) off[f] = reinterpret_cast<int64_t *>(c->d_foff + f * ostride);
-  int64_t *bsum = reinterpret_cast<int64_t *>(c->d_foff + 4 * ostride);
-  int64_t *small = reinterpret_cast<int64_t *>(c->d_foff + 4 * ostride + up(4 * nblk * 8));  // [0] bad, [1..4] totals
+  FieldOffs o;
+  HIPCHK(c, carve(c->d_foff, nullptr, [&](Carve &k) { o = field_offs(k, (size_t)n, (size_t)field_size_blocks(n)); }));
   const RecordColumnsDev &k = c->rcols;
   const FieldSizesArgs sa{c->d_roff + i0, k.block_size + i0, k.bin_mq_nl + i0, k.flag_nc + i0, k.l_seq + i0, n, c->L};
   {
     Timer t(c, "record_field_sizes");
-    HIPCHK(c, launch_field_sizes(sa, bsum, FieldOffsets{off[0], off[1], off[2], off[3]},
-                                 reinterpret_cast<unsigned long long *>(small), small + 1, c->stream));
+    HIPCHK(c, launch_field_sizes(sa, o.bsum, FieldOffsets{o.off[0], o.off[1], o.off[2], o.off[3]},
+                                 reinterpret_cast<unsigned long long *>(o.first_bad), o.totals, c->stream));
   }
-  int64_t h[5];
-  HIPCHK(c, hipMemcpyAsync(h, small, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  int64_t h[5];  // the first bad record and the four totals: one run
+  HIPCHK(c, hipMemcpyAsync(h, o.first_bad, sizeof(h), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (h[0] != -1) {  // the gather is not launched: it reads only records that passed
-    int64_t x = -1;
-    HIPCHK(c, hipMemcpy(&x, c->d_roff + i0 + h[0], 8, hipMemcpyDeviceToHost));
-    c->err.position = x;
-    return set_err(c, SBAM_ERR_RECORD, "record %lld at %lld: variable-length fields overrun block_size",
-                   (long long)(i0 + h[0]), (long long)x);
-  }
+  // (the gather is not launched: it reads only records that passed)
+  if (h[0] != -1) return bad_record(c, i0 + h[0], "variable-length fields overrun block_size");
   const sbam_record_field_totals tot{h[1], h[2], h[3], h[4]};
-  // data arena: the selected columns, each 256-B aligned and padded to the gather's 8-byte stores
+  // data arena: the selected columns
   const struct { uint32_t bit; int64_t bytes; int off; int sh; } col[5] = {
       {SBAM_FIELD_NAME, tot.name_bytes, 0, 0}, {SBAM_FIELD_CIGAR, 4 * tot.cigar_ops, 1, 2},
       {SBAM_FIELD_SEQ, tot.seq_bases, 2, 0},   {SBAM_FIELD_QUAL, tot.seq_bases, 2, 0},
       {SBAM_FIELD_AUX, tot.aux_bytes, 3, 0}};
-  // (behind each: the gather's per-tile record ranges)
-  size_t need = 0, at[5], tiles_at[5];
-  for (int f = 0; f < 5; f++) {
-    at[f] = tiles_at[f] = need;
-    if (!(fields & col[f].bit)) continue;
-    need += up((size_t)col[f].bytes + 8);
-    tiles_at[f] = need;
-    need += up((size_t)field_gather_tiles(col[f].bytes) * 16);
-  }
-  HIPCHK(c, c->d_fdata.ensure(need));
-  uint8_t *data[5];
+  int64_t col_bytes[5];
+  for (int f = 0; f < 5; f++) col_bytes[f] = (fields & col[f].bit) ? col[f].bytes : -1;
+  ByteCol d[5] = {};
+  HIPCHK(c, ensure_byte_columns(c->d_fdata, 5, col_bytes, d));
   {
     Timer t(c, "record_fields");
     for (int f = 0; f < 5; f++) {
-      data[f] = (fields & col[f].bit) ? c->d_fdata + at[f] : nullptr;
-      if (!data[f]) continue;
-      const FieldGatherArgs ga{c->d_u, sa.roff, sa.bin_mq_nl, sa.flag_nc, sa.l_seq, off[col[f].off],
-                               n,      col[f].sh, col[f].bytes, data[f],
-                               reinterpret_cast<int64_t *>(c->d_fdata + tiles_at[f])};
+      if (!d[f].data) continue;
+      const FieldGatherArgs ga{c->d_u, sa.roff,   sa.bin_mq_nl, sa.flag_nc, sa.l_seq, o.off[col[f].off],
+                               n,      col[f].sh, col[f].bytes, d[f].data,    d[f].tiles};
       HIPCHK(c, launch_field_gather(f, ga, c->stream));
     }
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->fdev = sbam_record_fields{off[0], data[0], off[1], reinterpret_cast<uint32_t *>(data[1]), off[2], data[2],
-                               data[3], off[3], data[4]};
+  c->fdev = sbam_record_fields{o.off[0], d[0].data, o.off[1], reinterpret_cast<uint32_t *>(d[1].data), o.off[2], d[2].data,
+                               d[3].data, o.off[3], d[4].data};
   c->f_tot = tot;
   c->f_i0 = i0;
   c->f_n = n;
@@ -1803,7 +1754,7 @@ int sbam_load_record_tags(sbam_ctx *c, int64_t i0, int64_t n, const sbam_tag_que
     wa.filter |= 1ull << sbam_tag::filter_bit(wa.key[j]);
   }
   HIPCHK(c, hipSetDevice(c->device));
-  c->t_n = -1;
+  HIPCHK(c, drop_from(c, kTags));
   c->tdev = sbam_record_tags{};
   c->t_tot = sbam_record_tag_totals{};
   if (totals) *totals = c->t_tot;
@@ -1814,50 +1765,37 @@ int sbam_load_record_tags(sbam_ctx *c, int64_t i0, int64_t n, const sbam_tag_que
     c->t_n = 0;
     return SBAM_OK;
   }
-  const TagLayout lay = tag_layout((size_t)n, (size_t)n_tags, (size_t)nb);
-  HIPCHK(c, ensure_tags(c, lay));
   const RecordColumnsDev &k = c->rcols;
-  uint8_t *cell = c->d_tcell, *ob = c->d_toff;
-  int64_t *small = reinterpret_cast<int64_t *>(ob + lay.small);  // [0] bad, [1 ..] byte totals, [1 + 32 ..] present slots
   wa.rec = FieldSizesArgs{c->d_roff + i0, k.block_size + i0, k.bin_mq_nl + i0, k.flag_nc + i0, k.l_seq + i0, n, c->L};
   wa.u = c->d_u;
   wa.nq = n_tags;
   wa.nb = nb;
-  wa.type = cell;
-  wa.sub = cell + lay.sub;
-  wa.rel = reinterpret_cast<int32_t *>(cell + lay.rel);
-  wa.value = reinterpret_cast<int64_t *>(cell + lay.value);
-  wa.off = reinterpret_cast<int64_t *>(ob);
-  wa.ostride = (int64_t)(lay.ostride / 8);
-  wa.src = reinterpret_cast<int64_t *>(ob + lay.src);
-  wa.first_bad = reinterpret_cast<unsigned long long *>(small);
-  wa.present = wa.first_bad + 1 + SBAM_MAX_TAGS;
+  TagScan o;
+  HIPCHK(c, carve(c->d_tcell, nullptr, [&](Carve &k) { tag_cells(k, wa, (size_t)n); }));
+  HIPCHK(c, carve(c->d_toff, nullptr,
+                  [&](Carve &k) { o = tag_offs(k, wa, n, exclusive_scan_blocks(n), kTagPresentSlots); }));
+  const size_t small_words = kTagPresentAt + kTagPresentSlots * SBAM_MAX_TAGS;  // (the run at wa.first_bad)
   {
     Timer t(c, "record_tag_walk");
-    HIPCHK(c, hipMemsetAsync(small, 0, kTagSmallWords * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(small, 0xff, 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(wa.first_bad, 0, small_words * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(wa.first_bad, 0xff, 8, c->stream));
     HIPCHK(c, launch_tag_walk(wa, c->stream));
-    HIPCHK(c, launch_exclusive_scan(wa.off, wa.ostride, n, nb, reinterpret_cast<int64_t *>(ob + lay.bsum),
-                                    small + 1, c->stream));
+    HIPCHK(c, launch_exclusive_scan(wa.off, wa.ostride, n, nb, o.bsum, o.totals, c->stream));
   }
-  std::vector<int64_t> h(kTagSmallWords);
-  HIPCHK(c, hipMemcpyAsync(h.data(), small, kTagSmallWords * 8, hipMemcpyDeviceToHost, c->stream));
+  std::vector<int64_t> h(small_words);
+  HIPCHK(c, hipMemcpyAsync(h.data(), wa.first_bad, small_words * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (h[0] != -1) {  // nothing is produced; the gather is not launched
-    int64_t x = -1;
-    HIPCHK(c, hipMemcpy(&x, c->d_roff + i0 + h[0], 8, hipMemcpyDeviceToHost));
-    c->err.position = x;
-    return set_err(c, SBAM_ERR_RECORD, "record %lld at %lld: malformed tag list, or variable-length fields overrun block_size",
-                   (long long)(i0 + h[0]), (long long)x);
-  }
+  // (nothing is produced; the gather is not launched)
+  if (h[0] != -1)
+    return bad_record(c, i0 + h[0], "malformed tag list, or variable-length fields overrun block_size");
   sbam_record_tag_totals tot{};
   int64_t col_bytes[SBAM_MAX_TAGS];
   for (int j = 0; j < n_tags; j++) {
-    for (int s = 0; s < kTagPresentSlots; s++) tot.present[j] += h[1 + SBAM_MAX_TAGS + s * SBAM_MAX_TAGS + j];
-    if (wa.bcol[j] >= 0) tot.bytes[j] = col_bytes[wa.bcol[j]] = h[1 + wa.bcol[j]];
+    for (int s = 0; s < kTagPresentSlots; s++) tot.present[j] += h[kTagPresentAt + s * SBAM_MAX_TAGS + j];
+    if (wa.bcol[j] >= 0) tot.bytes[j] = col_bytes[wa.bcol[j]] = h[kTagTotalsAt + wa.bcol[j]];
   }
-  size_t at[SBAM_MAX_TAGS], tiles_at[SBAM_MAX_TAGS];
-  HIPCHK(c, ensure_tag_bytes(c, col_bytes, nb, at, tiles_at));
+  ByteCol d[SBAM_MAX_TAGS] = {};
+  HIPCHK(c, ensure_byte_columns(c->d_tdata, nb, col_bytes, d));
   sbam_record_tags dev{wa.type, wa.sub, wa.rel, wa.value, {}, {}};
   {
     Timer t(c, "record_tag_bytes");
@@ -1865,9 +1803,9 @@ int sbam_load_record_tags(sbam_ctx *c, int64_t i0, int64_t n, const sbam_tag_que
       const int b = wa.bcol[j];
       if (b < 0) continue;
       dev.bytes_off[j] = wa.off + b * wa.ostride;
-      dev.bytes[j] = c->d_tdata + at[b];
+      dev.bytes[j] = d[b].data;
       FieldGatherArgs ga{c->d_u, nullptr, nullptr, nullptr, nullptr, dev.bytes_off[j], n, 0, col_bytes[b], dev.bytes[j],
-                         reinterpret_cast<int64_t *>(c->d_tdata + tiles_at[b])};
+                         d[b].tiles};
       ga.src = wa.src + b * n;
       HIPCHK(c, launch_field_gather(5, ga, c->stream));
     }
@@ -1933,15 +1871,14 @@ int sbam_build_index(sbam_ctx *c, sbam_index_totals *totals) {
     return set_err(c, SBAM_ERR_STATE, "sbam_build_index needs sbam_load_records over every split of the file");
   if (int rc = ensure_blocks(c)) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  c->idx_built = false;
+  HIPCHK(c, drop_from(c, kIndex));
   const int64_t N = no_records ? 0 : c->n_loaded;
   const int32_t nref = c->nref;
   HIPCHK(c, ensure_index(c, (size_t)N));
-  const size_t nstat = 4 + 5 * (size_t)nref;
-  HIPCHK(c, c->d_istat.ensure(nstat));
+  IndexStats &st = c->istat;
+  HIPCHK(c, carve(c->d_istat, nullptr, [&](Carve &k) { st = index_words<IndexStats>(k, (size_t)nref); }));
   HIPCHK(c, c->d_iintv.ensure((size_t)nref + 1));
-  unsigned long long *w = c->d_istat;
-  const IndexStats st{w, w + 4, w + 4 + nref, w + 4 + 2 * (size_t)nref, w + 4 + 3 * (size_t)nref, w + 4 + 4 * (size_t)nref};
+  const size_t nstat = st.n_intv + nref - st.w;  // (one run)
   const RecordColumnsDev &k = c->rcols;
   const IndexArgs ia{c->d_u,  c->L,        c->d_roff, k.block_pos, k.block_off, k.block_size, k.ref_id,
                      k.pos,   k.bin_mq_nl, k.flag_nc, N,           nref,        c->d_bstart,  c->d_buoff,
@@ -1949,11 +1886,11 @@ int sbam_build_index(sbam_ctx *c, sbam_index_totals *totals) {
   std::vector<unsigned long long> hs(nstat, 0);
   {
     Timer t(c, "index");
-    HIPCHK(c, hipMemsetAsync(w, 0, nstat * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(w, 0xff, 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(st.w, 0, nstat * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(st.w, 0xff, 8, c->stream));
     if (nref) HIPCHK(c, hipMemsetAsync(st.off_beg, 0xff, (size_t)nref * 8, c->stream));
     HIPCHK(c, launch_index_pass1(ia, st, c->d_iheads, c->stream));
-    HIPCHK(c, hipMemcpyAsync(hs.data(), w, nstat * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hs.data(), st.w, nstat * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (hs[0] != ~0ull) {
       c->err.position = (int64_t)hs[0];
@@ -1962,7 +1899,7 @@ int sbam_build_index(sbam_ctx *c, sbam_index_totals *totals) {
     }
     const int64_t n_runs = (int64_t)hs[3];
     c->idx_intv.assign((size_t)nref + 1, 0);
-    for (int32_t r = 0; r < nref; r++) c->idx_intv[r + 1] = c->idx_intv[r] + (int64_t)hs[4 + 4 * (size_t)nref + r];
+    for (int32_t r = 0; r < nref; r++) c->idx_intv[r + 1] = c->idx_intv[r] + (int64_t)hs[st.n_intv - st.w + r];
     const int64_t n_intv = c->idx_intv[nref];
     HIPCHK(c, c->d_irunref.ensure((size_t)n_runs));
     HIPCHK(c, c->d_irunbin.ensure((size_t)n_runs));
@@ -2001,14 +1938,13 @@ int sbam_get_index_refs(sbam_ctx *c, int64_t *intv_off, uint64_t *ioffset, uint6
   HIPCHK(c, hipSetDevice(c->device));
   const size_t nref = (size_t)c->idx_tot.n_ref, nb = nref * 8;
   if (intv_off) std::copy(c->idx_intv.begin(), c->idx_intv.end(), intv_off);
-  const unsigned long long *w = c->d_istat.get() + 4;
   if (ioffset && c->idx_tot.n_intv_total)
     HIPCHK(c, hipMemcpyAsync(ioffset, c->d_ioff, (size_t)c->idx_tot.n_intv_total * 8, hipMemcpyDeviceToHost, c->stream));
   if (nref) {
-    if (n_mapped) HIPCHK(c, hipMemcpyAsync(n_mapped, w, nb, hipMemcpyDeviceToHost, c->stream));
-    if (n_unmapped) HIPCHK(c, hipMemcpyAsync(n_unmapped, w + nref, nb, hipMemcpyDeviceToHost, c->stream));
-    if (off_beg) HIPCHK(c, hipMemcpyAsync(off_beg, w + 2 * nref, nb, hipMemcpyDeviceToHost, c->stream));
-    if (off_end) HIPCHK(c, hipMemcpyAsync(off_end, w + 3 * nref, nb, hipMemcpyDeviceToHost, c->stream));
+    if (n_mapped) HIPCHK(c, hipMemcpyAsync(n_mapped, c->istat.n_mapped, nb, hipMemcpyDeviceToHost, c->stream));
+    if (n_unmapped) HIPCHK(c, hipMemcpyAsync(n_unmapped, c->istat.n_unmapped, nb, hipMemcpyDeviceToHost, c->stream));
+    if (off_beg) HIPCHK(c, hipMemcpyAsync(off_beg, c->istat.off_beg, nb, hipMemcpyDeviceToHost, c->stream));
+    if (off_end) HIPCHK(c, hipMemcpyAsync(off_end, c->istat.off_end, nb, hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SBAM_OK;
@@ -2150,12 +2086,11 @@ int sbam_write_bam(sbam_ctx *c, const sbam_write_args *a, sbam_write_totals *tot
   if (a->with_header && (c->base != 0 || c->header_x < 0))
     return set_err(c, SBAM_ERR_STATE, "with_header needs a context that starts at file offset 0 and has read its header");
   HIPCHK(c, hipSetDevice(c->device));
-  c->w.ubytes = -1;
+  HIPCHK(c, drop_from(c, kWritten));
   const int64_t header_bytes = a->with_header ? c->header_x : 0;
-  const WriteSelLayout sl = write_sel_layout((size_t)N);
-  HIPCHK(c, c->d_wsel.ensure(sl.words));
+  WriteSel sl;
+  HIPCHK(c, carve(c->d_wsel, nullptr, [&](Carve &k) { sl = write_sel(k, N, exclusive_scan_blocks(N + 1)); }));
   HIPCHK(c, c->d_wrange.ensure((size_t)(2 * a->n_ranges)));
-  int64_t *len = c->d_wsel, *cnt = len + sl.stride, *src = len + sl.src, *bsum = len + sl.bsum, *tot = len + sl.tot;
   if (a->n_ranges) {
     HIPCHK(c, hipMemcpyAsync(c->d_wrange, a->range_lo, (size_t)a->n_ranges * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_wrange + a->n_ranges, a->range_hi, (size_t)a->n_ranges * 8, hipMemcpyHostToDevice,
@@ -2164,12 +2099,12 @@ int sbam_write_bam(sbam_ctx *c, const sbam_write_args *a, sbam_write_totals *tot
   {
     Timer t(c, "write_select");
     const WriteSelectArgs sa{c->d_roff, c->rcols.block_size, N, c->L, c->d_wrange, c->d_wrange + a->n_ranges,
-                             a->n_ranges, a->keep_device, header_bytes, len, cnt, src};
+                             a->n_ranges, a->keep_device, header_bytes, sl.len, sl.cnt, sl.src};
     HIPCHK(c, launch_write_select(sa, c->stream));
-    HIPCHK(c, launch_exclusive_scan(len, (int64_t)sl.stride, N + 1, 2, bsum, tot, c->stream));
+    HIPCHK(c, launch_exclusive_scan(sl.len, (int64_t)sl.stride, N + 1, 2, sl.bsum, sl.tot, c->stream));
   }
   int64_t h[2] = {0, 0};
-  HIPCHK(c, hipMemcpyAsync(h, tot, 16, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h, sl.tot, 16, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const int64_t ubytes = h[0], n_records = h[1];
   HIPCHK(c, ensure_write_stream(c->w, ubytes));
@@ -2177,15 +2112,17 @@ int sbam_write_bam(sbam_ctx *c, const sbam_write_args *a, sbam_write_totals *tot
   {
     Timer t(c, "write_gather");
     // every entry is a "field" at src[i] of len[i] bytes: sbam_fields.hip's gather, divided over output bytes
-    const FieldGatherArgs ga{c->d_u, nullptr, nullptr, nullptr, nullptr, len, N + 1, 0, ubytes, c->w.u, c->d_wtiles, src};
+    const FieldGatherArgs ga{c->d_u, nullptr, nullptr, nullptr, nullptr, sl.len,       N + 1,
+                             0,      ubytes,  c->w.u,  c->d_wtiles, sl.src};
     HIPCHK(c, launch_field_gather(5, ga, c->stream));
   }
   HIPCHK(c, writer_run(c->w, c->stream, c, ubytes, bb, a->level, a->with_eof != 0));
   HIPCHK(c, c->d_wrpos.ensure((size_t)n_records));
   HIPCHK(c, c->d_wroff.ensure((size_t)n_records));
-  HIPCHK(c, launch_written_records(len, cnt, N, bb, c->w.start, c->d_wrpos, c->d_wroff, c->stream));
+  HIPCHK(c, launch_written_records(sl.len, sl.cnt, N, bb, c->w.start, c->d_wrpos, c->d_wroff, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->w_tot = sbam_write_totals{n_records, header_bytes, ubytes, c->w.nb, c->w.n_stored, c->w.comp_bytes};
+  c->w.ubytes = ubytes;
   if (totals) *totals = c->w_tot;
   return SBAM_OK;
 }
@@ -2215,10 +2152,10 @@ int sbam_get_written_blocks(sbam_ctx *c, int64_t *start, int32_t *csize, int32_t
   const size_t nb = (size_t)c->w.nb;
   if (!nb) return SBAM_OK;
   HIPCHK(c, hipSetDevice(c->device));
-  const int32_t *cs = c->w.cols + 2 * nb, *us = cs + nb;
+  const WriteCols &col = c->w.col;
   if (start) HIPCHK(c, hipMemcpy(start, c->w.start, nb * 8, hipMemcpyDeviceToHost));
-  if (csize) HIPCHK(c, hipMemcpy(csize, cs, nb * 4, hipMemcpyDeviceToHost));
-  if (usize) HIPCHK(c, hipMemcpy(usize, us, nb * 4, hipMemcpyDeviceToHost));
+  if (csize) HIPCHK(c, hipMemcpy(csize, col.csize, nb * 4, hipMemcpyDeviceToHost));
+  if (usize) HIPCHK(c, hipMemcpy(usize, col.usize, nb * 4, hipMemcpyDeviceToHost));
   return SBAM_OK;
 }
 

@@ -622,6 +622,8 @@ class BamFile:
     def inflate(self) -> int:
         n = ctypes.c_int64(0)
         self._crc = None
+        self.n_loaded = 0  # (a new stream: the context drops what was made from the old one)
+        self._index = self._written = None
         self._check(self.L.sbam_inflate(self.ctx, ctypes.byref(n)))
         if self.verify_crc and self.n_blocks is not None:  # (the context checked the whole table)
             self._crc = (0, int(self.n_blocks))

@@ -432,3 +432,43 @@ def test_block_table_before_inflate_gpu(name):
         assert np.array_equal(st, o.start[k0:]) and np.array_equal(cs, o.csize[k0:])
         assert np.array_equal(us, o.usize[k0:]) and np.array_equal(uo, o.uoff[k0:-1] - o.uoff[k0])
         assert f.inflate() == o.L - int(o.uoff[k0])
+
+
+@pytest.mark.gpu
+def test_new_stream_or_table_drops_what_was_made_from_the_old_one_gpu():
+    """One stage rule: a second inflate leaves no records, fields, tags, index or written BAM (their source, the
+    stream, was overwritten), and a second block scan leaves no stream; each getter answers SBAM_ERR_STATE until its
+    stage has run again, and the stages run again give what they gave the first time."""
+    import ctypes
+    import numpy as np
+    import sbam
+    from conftest import fixture_bytes
+    L = sbam.load_library()
+    with sbam.BamFile(fixture_bytes("2.100-1000.bam")) as f:
+        stream = f.read_uncompressed(0, f.uncompressed_size)
+        sizes, cols = f.load_records(100000)
+        assert f.n_loaded == sizes.sum() > 0
+        f.load_record_fields()
+        f.load_record_tags(["NM"])
+        f.build_index(100000)
+        f.write_bam()
+        getters = {
+            "columns": lambda: L.sbam_get_record_columns(f.ctx, 0, 0, ctypes.byref(sbam._RecordColumns())),
+            "fields": lambda: L.sbam_get_record_fields(f.ctx, ctypes.byref(sbam._RecordFields())),
+            "tags": lambda: L.sbam_get_record_tags(f.ctx, ctypes.byref(sbam._RecordTags())),
+            "index": lambda: L.sbam_get_index_runs(f.ctx, None, None, None, None),
+            "written": lambda: L.sbam_get_written(f.ctx, None, 0)}
+        assert {k: g() for k, g in getters.items() if k != "written"} == dict.fromkeys(
+            ["columns", "fields", "tags", "index"], sbam.SBAM_OK)
+        assert getters["written"]() == sbam.ERR_ARG  # (held, and larger than no bytes)
+        assert f.inflate() == len(stream)
+        assert {k: g() for k, g in getters.items()} == dict.fromkeys(getters, sbam.ERR_STATE)
+        assert f.n_loaded == 0 and f._index is None and f._written is None
+        s2, c2 = f.load_records(100000)
+        assert np.array_equal(s2, sizes) and cols.keys() == c2.keys()
+        assert all(np.array_equal(c2[k], cols[k]) for k in cols)
+        f.n_blocks = f._scan()
+        assert L.sbam_read_uncompressed(f.ctx, 0, 0, None) == sbam.ERR_STATE
+        assert getters["columns"]() == sbam.ERR_STATE
+        assert f.inflate() == len(stream)
+        assert f.read_uncompressed(0, len(stream)) == stream
