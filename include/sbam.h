@@ -132,6 +132,17 @@ int sbam_find_block_starts(sbam_ctx *ctx, const int64_t *starts, int64_t n, int3
  * *n_blocks receives the block count. */
 int sbam_scan_blocks(sbam_ctx *ctx, int64_t *n_blocks);
 
+/* Which way the last sbam_scan_blocks took to its table (read-only; no reference counterpart):
+ *   *followed   1 when the table came from following the headers' BSIZE hops in parallel segments;
+ *   *fell_back  1 when that was tried and not accepted (a segment's speculative entry was not on the chain, a parse
+ *               failure, more blocks in a segment than its slots), and the byte scan built the table instead;
+ *   *segments   the segments followed (0 when following was not tried: a candidate list already existed, or
+ *               SBAM_SCAN_FOLLOW=0 in the environment).
+ * All 0 before a scan.  Any pointer may be NULL. */
+int sbam_scan_path(sbam_ctx *ctx, int32_t *followed, int32_t *fell_back, int64_t *segments);
+/* Bytes per segment of that path (a build constant; tests place headers at segment edges). */
+int sbam_follow_segment_bytes(void);
+
 /* Copy the block table (IndexBlocks format: start, compressedSize, uncompressedSize;
  * bgzf/.../index/IndexBlocks.scala:40-44) plus each block's offset in the uncompressed stream. */
 int sbam_get_blocks(sbam_ctx *ctx, int64_t *start, int32_t *csize, int32_t *usize, int64_t *uoff, int64_t cap);

@@ -205,6 +205,8 @@ struct BlockMirror {
 // The context's small device scratch: one 8-byte word per use, so that no two uses share a word by accident.
 //   scan_total, scan_overflow  scan_candidates (read back as one pair)
 //   table_first, chain_stop    sbam_scan_blocks: the lower bound, and where the chain verify stopped
+//   follow_bad, follow_stop,   follow_blocks: the link kernel's verdict and the accepted table's block count (read
+//   follow_total               back as one triple)
 //   inflate_error              first block whose status is not 0
 //   record_count, proof_fail   sbam_record_offsets; split_counts (an int32 flag)
 //   arena_used                 TokPool::arena_used
@@ -212,6 +214,7 @@ struct BlockMirror {
 struct Scratch {
   int64_t scan_total, scan_overflow, table_first, chain_stop, inflate_error, record_count, proof_fail, arena_used;
   int64_t crc_bad, crc_first_bad;
+  int64_t follow_bad, follow_stop, follow_total;
 };
 
 }  // namespace
@@ -226,7 +229,11 @@ struct sbam_ctx {
   int64_t ncand = -1;
   DevBuf<int32_t> d_cc;
   DevBuf<int64_t> d_coff;
-  DevBuf<Candidate> d_slots;  // one-pass scan: kScanSlots per chunk
+  DevBuf<Candidate> d_slots;  // one-pass scan: kScanSlots per chunk; the followed table: kFollowSlots per segment
+  // the followed table's segments (follow_segs), and what the last sbam_scan_blocks did (sbam_scan_path)
+  DevBuf<uint8_t> d_fseg;
+  int32_t sp_followed = 0, sp_fell_back = 0;
+  int64_t sp_segments = 0;
   // per-call query scratch (split starts / answers): kept, since hipMalloc + hipFree per call cost ~0.5 ms of
   // host time each (a device-wide synchronisation) between the kernels of a step
   DevBuf<int64_t> d_qa, d_qb;
@@ -393,8 +400,10 @@ void set_bitmap(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, bool list_form) 
 void drop_bitmap(sbam_ctx *c) { c->bm_valid = c->bm_list = c->rp_fetch = false; }
 
 // The stages a context can hold, in the order they are made: candidates -> table -> stream -> {crc, bitmap, records},
-// records -> {fields, tags, index, written}.  A producer drops its own stage, and with it everything made from it,
-// before it touches a buffer (drop_from), and sets its stage's validity field as its last step; nothing else clears one.
+// records -> {fields, tags, index, written}.  (The table comes from the followed hops, or from the candidates; a
+// context can hold one without the candidates, never a later stage without the table.)  A producer drops its own
+// stage, and with it everything made from it, before it touches a buffer (drop_from), and sets its stage's validity
+// field as its last step; nothing else clears one.
 enum Stage { kCandidates, kTable, kStream, kCrc, kBitmap, kRecords, kFields, kTags, kIndex, kWritten };
 bool any_stage_ran(const sbam_ctx *c) { return c->ncand >= 0 || c->blk.n >= 0 || c->L >= 0 || c->n_loaded >= 0; }
 // Returns the table mirror's invalidate() (a wait for a copy in flight), hipSuccess for every other stage.
@@ -402,6 +411,7 @@ hipError_t drop_from(sbam_ctx *c, Stage from) {
   const bool stream = from <= kStream, records = stream || from == kRecords;
   if (from == kCandidates) c->ncand = -1;
   const hipError_t e = from <= kTable ? c->blk.invalidate() : hipSuccess;
+  if (from <= kTable) c->sp_followed = c->sp_fell_back = 0, c->sp_segments = 0;
   if (stream) c->L = c->inflate_slow = -1;
   if (stream || from == kCrc) c->crc_b0 = c->crc_b1 = -1;
   if (stream || from == kBitmap) drop_bitmap(c);
@@ -422,6 +432,12 @@ hipError_t ensure_scan(sbam_ctx *c, int64_t comp_bytes, bool *grew = nullptr) {
   HIPTRY(c->d_cc.ensure(nchunks, grew));
   HIPTRY(c->d_coff.ensure(nchunks, grew));
   return c->d_slots.ensure((size_t)nchunks * kScanSlots, grew);
+}
+// the followed table of comp_bytes: its segments' words, and their rows in the scan's slots
+hipError_t ensure_follow(sbam_ctx *c, int64_t nseg, bool *grew = nullptr, FollowSegs *fs = nullptr) {
+  HIPTRY(c->d_slots.ensure((size_t)nseg * kFollowSlots, grew));
+  FollowSegs r;
+  return carve(c->d_fseg, grew, [&](Carve &k) { (fs ? *fs : r) = follow_segs<FollowSegs>(k, (size_t)nseg); });
 }
 hipError_t ensure_table(sbam_ctx *c, int64_t nb, bool *grew = nullptr) {
   HIPTRY(c->d_bstart.ensure(nb + 1, grew));
@@ -724,6 +740,7 @@ int sbam_reserve(sbam_ctx *c, int64_t comp_bytes, int64_t n_blocks, int64_t ubyt
   // device memory.  The resident compressed bytes and the contig lengths are kept.
   bool grew = false;
   HIPCHK(c, ensure_scan(c, comp_bytes, &grew));
+  HIPCHK(c, ensure_follow(c, follow_segments(comp_bytes, 0), &grew));
   // candidates: every block's header plus the rare false positives inside payloads
   HIPCHK(c, c->d_cand.ensure((size_t)(n_blocks + n_blocks / 8 + 1024), &grew));
   HIPCHK(c, ensure_table(c, n_blocks, &grew));
@@ -783,11 +800,60 @@ static int scan_candidates(sbam_ctx *c) {
   return SBAM_OK;
 }
 
+// ---- the table without candidates (follow) -----------------------------------------------------------
+// SBAM_SCAN_FOLLOW=0: build every table from the byte scan (tests and A/B runs of the two paths)
+static bool follow_enabled() {
+  const char *e = std::getenv("SBAM_SCAN_FOLLOW");
+  return !(e && *e == '0');
+}
+
+// The block table from start_rel by following the BSIZE hops in parallel segments.  *nb: its blocks, with the device
+// columns built and the host's copy queued as after the fast chain; -1 when the segments' chains do not join up into
+// one accepted table (sp_fell_back is set, nothing else is changed, and the caller runs the byte scan).
+static int follow_blocks(sbam_ctx *c, int64_t start_rel, int64_t *nb) {
+  const int64_t nseg = follow_segments(c->D, start_rel);
+  FollowSegs fs;
+  unsigned long long v[3] = {0, 0, 0};  // first unusable segment, first stopped segment, rows up to the stop
+  {
+    Timer t(c, "scan");
+    HIPCHK(c, ensure_follow(c, nseg, nullptr, &fs));
+    HIPCHK(c, launch_follow_blocks(c->d_comp, c->D, start_rel, nseg, fs, c->d_slots, SMALL(c, follow_bad), c->stream));
+    HIPCHK(c, launch_scan_sums(fs.cnt, fs.off, nseg, 1, SMALL(c, follow_total), c->stream));
+    HIPCHK(c, hipMemcpyAsync(v, SMALL(c, follow_bad), sizeof(v), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (the one round trip: the table's size)
+  }
+  c->sp_segments = nseg;
+  if (!(v[1] < v[0])) {  // no stop before the first segment that cannot be used
+    c->sp_fell_back = 1;
+    *nb = -1;
+    return SBAM_OK;
+  }
+  const int64_t n = (int64_t)v[2];
+  Timer t(c, "chain");
+  HIPCHK(c, c->d_cand.ensure((size_t)n));  // (no candidate list lives there: ncand < 0)
+  HIPCHK(c, ensure_table(c, n));
+  HIPCHK(c, launch_follow_compact(c->d_slots, fs, nseg, c->d_cand, c->stream));
+  HIPCHK(c, launch_gather_blocks(c->d_cand, 0, n, c->d_bstart, c->d_bh, c->d_bc, c->d_bu, c->d_buoff + n + 1,
+                                 c->d_buoff, c->stream));
+  HIPCHK(c, c->blk.start_copy(c->d_bstart, c->d_buoff, c->d_bc, c->d_bu, n, c->stream));
+  c->sp_followed = 1;
+  *nb = n;
+  return SBAM_OK;
+}
+
+int sbam_follow_segment_bytes(void) { return kFollowSeg; }
+
+int sbam_scan_path(sbam_ctx *c, int32_t *followed, int32_t *fell_back, int64_t *segments) {
+  if (!c) return SBAM_ERR_ARG;
+  if (followed) *followed = c->sp_followed;
+  if (fell_back) *fell_back = c->sp_fell_back;
+  if (segments) *segments = c->sp_segments;
+  return SBAM_OK;
+}
+
 int sbam_find_block_starts(sbam_ctx *c, const int64_t *starts, int64_t n, int32_t nchk, int64_t *out) {
   if (!c || (!starts && n) || (!out && n) || nchk < 0) return SBAM_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  int rc = scan_candidates(c);
-  if (rc) return rc;
   std::vector<int64_t> rel(n);
   for (int64_t i = 0; i < n; i++) {
     rel[i] = starts[i] - c->base;
@@ -797,7 +863,10 @@ int sbam_find_block_starts(sbam_ctx *c, const int64_t *starts, int64_t n, int32_
   HIPCHK(c, c->d_qb.ensure((size_t)n));
   int64_t *d_q = c->d_qa, *d_o = c->d_qb;
   HIPCHK(c, hipMemcpyAsync(d_q, rel.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, launch_find_block_starts(c->d_comp, c->D, c->d_cand, c->ncand, d_q, n, nchk, d_o, c->stream));
+  if (c->ncand >= 0)  // a candidate list exists: search it
+    HIPCHK(c, launch_find_block_starts(c->d_comp, c->D, c->d_cand, c->ncand, d_q, n, nchk, d_o, c->stream));
+  else  // none (the table was followed, or nothing has run): the same rules on the bytes behind each start
+    HIPCHK(c, launch_find_block_starts_bytes(c->d_comp, c->D, d_q, n, nchk, d_o, c->stream));
   HIPCHK(c, hipMemcpyAsync(out, d_o, n * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int64_t i = 0; i < n; i++) {
@@ -817,8 +886,7 @@ int sbam_scan_blocks(sbam_ctx *c, int64_t *n_blocks) {
   if (!c) return SBAM_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, drop_from(c, kTable));  // (no table, and nothing made from one, until this scan has built one)
-  int rc = scan_candidates(c);
-  if (rc) return rc;
+  int rc = SBAM_OK;
   int64_t start_rel = 0;
   if (c->base > 0) {  // a shard starts at the first block at/after its first byte
     int64_t s = c->base, o = 0;
@@ -826,6 +894,18 @@ int sbam_scan_blocks(sbam_ctx *c, int64_t *n_blocks) {
     if (rc) return rc;
     start_rel = o - c->base;
   }
+  if (c->ncand < 0 && follow_enabled()) {  // no candidate list yet: the table needs none
+    int64_t nb = -1;
+    rc = follow_blocks(c, start_rel, &nb);
+    if (rc) return rc;
+    if (nb >= 0) {
+      if (n_blocks) *n_blocks = nb;
+      return SBAM_OK;
+    }
+  }
+  // today's exact path, from the start: the candidates of every byte offset, then their chain
+  rc = scan_candidates(c);
+  if (rc) return rc;
   Timer t(c, "chain");
   int64_t first = 0;
   HIPCHK(c, launch_lower_bound(c->d_cand, c->ncand, start_rel, SMALL(c, table_first), c->stream));

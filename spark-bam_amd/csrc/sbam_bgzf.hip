@@ -322,6 +322,185 @@ __global__ __launch_bounds__(256) void k_block_uoff(const int32_t *__restrict__ 
 }
 
 // ================================================================================================
+// 2. The block table by following BSIZE hops (no pass over the bytes)
+// ================================================================================================
+// MetadataStream reads one header, adds BSIZE + 1 and reads the next: 18 + 4 bytes per block, not the block.  One such
+// chain is serial, so the loaded bytes are cut into segments of kFollowSeg bytes and one wave follows each: segment 0
+// from the table's first block, segment g > 0 from the first header pattern at or after g * kFollowSeg whose successor
+// holds the pattern too (a speculative entry).  k_follow_link then accepts the table only when every segment's exit
+// is the next one's entry up to the first stop; otherwise the byte scan above runs instead (a false header in a
+// payload that sits first behind a segment's edge costs exactly that).  No wave waits for another.
+
+// The header at q (q <= D) and the four bytes before it, which are the previous block's ISIZE: 28 bytes from the
+// aligned dword at or before q - 4, all inside [0, D + kCompPad).
+struct HeaderAt {
+  uint32_t magic, bc, xlen, bsize, prev_isize;
+  SB_DEV bool pattern() const { return magic == 0x04088b1fu && bc == 0x00024342u; }  // Header.make's seven bytes
+  SB_DEV int32_t hsize() const { return 18 + (int32_t)xlen - 6; }
+  SB_DEV int32_t csize() const { return (int32_t)bsize + 1; }
+  SB_DEV bool empty() const { return csize() - hsize() - 8 == 2; }
+};
+SB_DEV HeaderAt header_at(const uint8_t *d, int64_t q) {
+  const int64_t base = (q >= 4 ? q - 4 : 0) & ~(int64_t)3;
+  const uint32_t sh = (uint32_t)(q - base);  // 0..7; below 4 only for q < 4 (no block before it)
+  const uint32_t *p = reinterpret_cast<const uint32_t *>(d + base);
+  uint32_t w[7], v[6];
+#pragma unroll
+  for (int k = 0; k < 7; k++) w[k] = p[k];
+#pragma unroll
+  for (int k = 0; k < 6; k++) v[k] = __builtin_amdgcn_alignbyte(w[k + 1], w[k], sh & 3);
+  const bool hi = sh >= 4;
+  HeaderAt h;
+  h.prev_isize = v[0];
+  h.magic = hi ? v[1] : v[0];
+  h.xlen = (hi ? v[3] : v[2]) >> 16;
+  h.bc = (hi ? v[4] : v[3]) & 0x00ffffffu;
+  h.bsize = (hi ? v[5] : v[4]) & 0xffffu;
+  return h;
+}
+
+// First p in [lo, hi) (hi <= D - 17) that holds the header pattern and that accept(p) takes, in file order; -1: none.
+// The whole wave calls it with the same arguments: 1 KiB per load instruction (each lane its 16 positions' 32 bytes),
+// four of them in flight; accept runs wave-uniform on the rare hits.  hi - lo <= 64 KiB + 16: at most 17 iterations.
+template <class F>
+SB_DEV int64_t wave_first_header(const uint8_t *d, int64_t D, int64_t lo, int64_t hi, F accept) {
+  constexpr int kInFlight = 4;
+  for (int64_t base = lo & ~(int64_t)15; base < hi; base += kInFlight * 1024) {
+    uint32_t w[kInFlight][8];
+#pragma unroll
+    for (int k = 0; k < kInFlight; k++) {
+      const int64_t q0 = base + k * 1024 + lane_id() * 16;
+      if (q0 < hi) load32(d, q0, w[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < kInFlight; k++) {
+      const int64_t q0 = base + k * 1024 + lane_id() * 16;
+      uint32_t bits = 0;
+      if (q0 < hi) {
+        bits = header_bits16(w[k], q0, D);
+        if (q0 < lo) bits &= ~0u << (lo - q0);
+        if (q0 + 16 > hi) bits &= (1u << (hi - q0)) - 1u;
+      }
+      for (unsigned long long any = __ballot(bits != 0); any; any = __ballot(bits != 0)) {
+        const int l = __ffsll(any) - 1;
+        const uint32_t b = (uint32_t)__shfl((int)bits, l, 64);
+        const int i = __ffs(b) - 1;
+        const int64_t p = base + k * 1024 + l * 16 + i;
+        if (accept(p)) return p;
+        if (lane_id() == l) bits &= bits - 1;
+      }
+    }
+  }
+  return -1;
+}
+
+// One wave per segment.  Rows go to the segment's kFollowSlots fixed slots (a row past them is counted, not written,
+// and sets FOLLOW_OVERFLOW); a row's isize arrives with the next header's load, four bytes before it.
+__global__ __launch_bounds__(256) void k_follow_blocks(const uint8_t *__restrict__ d, int64_t D, int64_t start_rel,
+                                                        int64_t nseg, FollowSegs fs, Candidate *__restrict__ slots) {
+  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w >= nseg) return;
+  const int64_t g = start_rel / kFollowSeg + w;  // (the table's first block may lie past segment 0 of the bytes)
+  const int64_t seg_end = (g + 1) * (int64_t)kFollowSeg;
+  Candidate *out = slots + w * kFollowSlots;
+  int64_t q = start_rel;
+  if (w > 0) {
+    const int64_t lo = g * (int64_t)kFollowSeg;
+    q = wave_first_header(d, D, lo, min(lo + 65536, D - 17), [&](int64_t p) {
+      const HeaderAt h = header_at(d, p);
+      const int64_t nx = p + h.csize();
+      if (nx > D || h.empty() || nx + 18 > D) return true;  // the chain stops here: MetadataStream's rules
+      return header_at(d, nx).pattern();
+    });
+  }
+  const int64_t entry = q;
+  int32_t n = 0, kind = q < 0 ? FOLLOW_NOENTRY : 0;
+  // q grows by csize >= 1 per hop and ends the loop at seg_end: at most kFollowSeg + 1 hops
+  while (q >= 0) {
+    const HeaderAt h = header_at(d, q);  // (q <= D)
+    if (n > 0 && n <= kFollowSlots && lane_id() == 0) out[n - 1].isize = (int32_t)h.prev_isize;
+    if (q + 18 > D) { kind |= FOLLOW_STOP; break; }  // EOF inside the next header
+    if (q >= seg_end) break;
+    if (!h.pattern()) { kind |= FOLLOW_PARSE; break; }
+    if (q + h.csize() > D || h.empty()) { kind |= FOLLOW_STOP; break; }  // stop before emitting
+    if (n < kFollowSlots) {
+      if (lane_id() == 0) {
+        out[n].pos = q;
+        out[n].hsize = h.hsize();
+        out[n].csize = h.csize();
+        out[n].flags = CAND_ISIZE;
+      }
+    } else {
+      kind |= FOLLOW_OVERFLOW;
+    }
+    n++;
+    q += h.csize();
+  }
+  if (lane_id() == 0) {
+    fs.entry[w] = entry;
+    fs.exit[w] = q;
+    fs.rows[w] = n;
+    fs.kind[w] = kind;
+  }
+}
+
+// verdict[0] = first segment the table cannot be taken from (parse failure, overflow, no entry, or an exit that is
+// not the next segment's entry), verdict[1] = first segment whose chain stopped; both preset ~0.
+__global__ void k_follow_link(FollowSegs fs, int64_t nseg, unsigned long long *__restrict__ verdict) {
+  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= nseg) return;
+  const int32_t kind = fs.kind[w];
+  const bool stop = (kind & FOLLOW_STOP) != 0;
+  bool bad = (kind & (FOLLOW_PARSE | FOLLOW_OVERFLOW | FOLLOW_NOENTRY)) != 0;
+  if (!stop && !bad) bad = w + 1 >= nseg || fs.entry[w + 1] != fs.exit[w];
+  if (bad) atomicMin(verdict, (unsigned long long)w);
+  if (stop) atomicMin(verdict + 1, (unsigned long long)w);
+}
+// The accepted table's rows per segment (those up to the stop; none when the table is not accepted).
+__global__ void k_follow_counts(FollowSegs fs, int64_t nseg, const unsigned long long *__restrict__ verdict) {
+  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= nseg) return;
+  const unsigned long long bad = verdict[0], stop = verdict[1];
+  fs.cnt[w] = (stop < bad && (unsigned long long)w <= stop) ? fs.rows[w] : 0;
+}
+// slots -> file order, as k_scan_compact: row j of segment w goes to off[w] + j
+__global__ void k_follow_compact(const Candidate *__restrict__ slots, FollowSegs fs, int64_t nseg,
+                                 Candidate *__restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t w = i / kFollowSlots;
+  const int j = (int)(i % kFollowSlots);
+  if (w < nseg && j < fs.cnt[w]) out[fs.off[w] + j] = slots[i];
+}
+
+// FindBlockStart.apply without a candidate list: one wave per start.  k_find_block_starts' rules, with "a candidate
+// at cp" read as "the header test holds on the bytes at cp".
+__global__ __launch_bounds__(256) void k_find_block_starts_bytes(const uint8_t *__restrict__ d, int64_t D,
+                                                                  const int64_t *__restrict__ starts, int64_t nq,
+                                                                  int32_t nchk, int64_t *__restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= nq) return;
+  const int64_t s = starts[t];
+  int64_t best = s;  // nchk == 0: take(0) parses no header, so the first probe is accepted
+  if (nchk > 0) {
+    const int64_t lim = s + 65536;     // Block.MAX_BLOCK_SIZE probes
+    const int64_t qe = max(s, D - 17);  // q + 18 > D: EOF while reading the first header → accepted
+    best = wave_first_header(d, D, s, min(lim, qe), [&](int64_t p) {
+      int64_t cp = p;
+      for (int k = 0; k < nchk; k++) {
+        if (cp + 18 > D) break;
+        const HeaderAt h = header_at(d, cp);
+        if (!h.pattern()) return false;
+        if (cp + h.csize() > D || h.empty()) break;
+        cp += h.csize();
+      }
+      return true;
+    });
+    if (best < 0 && qe < lim) best = qe;
+  }
+  if (lane_id() == 0) out[t] = best;  // -1: HeaderSearchFailedException
+}
+
+// ================================================================================================
 // launch wrappers
 // ================================================================================================
 
@@ -365,6 +544,29 @@ hipError_t launch_find_block_starts(const uint8_t *, int64_t D, const Candidate 
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_find_block_starts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c, ncand, D, st, n,
                      nchk, out);
+  return hipGetLastError();
+}
+hipError_t launch_follow_blocks(const uint8_t *d, int64_t D, int64_t start_rel, int64_t nseg, FollowSegs fs,
+                                Candidate *slots, int64_t *verdict, hipStream_t s) {
+  unsigned long long *v = reinterpret_cast<unsigned long long *>(verdict);
+  (void)hipMemsetAsync(v, 0xff, 2 * sizeof(*v), s);
+  const unsigned nwg = (unsigned)((nseg + 255) / 256);
+  hipLaunchKernelGGL(k_follow_blocks, dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, s, d, D, start_rel, nseg, fs,
+                     slots);
+  hipLaunchKernelGGL(k_follow_link, dim3(nwg), dim3(256), 0, s, fs, nseg, v);
+  hipLaunchKernelGGL(k_follow_counts, dim3(nwg), dim3(256), 0, s, fs, nseg, v);
+  return hipGetLastError();
+}
+hipError_t launch_follow_compact(const Candidate *slots, FollowSegs fs, int64_t nseg, Candidate *out, hipStream_t s) {
+  const int64_t n = nseg * kFollowSlots;
+  hipLaunchKernelGGL(k_follow_compact, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, slots, fs, nseg, out);
+  return hipGetLastError();
+}
+hipError_t launch_find_block_starts_bytes(const uint8_t *d, int64_t D, const int64_t *st, int64_t n, int32_t nchk,
+                                          int64_t *out, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_find_block_starts_bytes, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, d, D, st, n, nchk,
+                     out);
   return hipGetLastError();
 }
 hipError_t launch_lower_bound(const Candidate *c, int64_t n, int64_t q, int64_t *out, hipStream_t s) {

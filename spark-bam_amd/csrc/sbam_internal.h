@@ -74,6 +74,33 @@ constexpr int kScanSlots = 512;      // candidate slots per chunk in the one-pas
 constexpr int kStreamPad = 16384;  // zero pad behind the uncompressed stream (>= checker LDS window)
 constexpr int kCompPad = 256;  // zero pad behind the compressed bytes (bit-reader / input-ring lookahead)
 
+// The block table by following BSIZE hops (sbam_bgzf.hip, section 2): bytes per segment (one wave each) and row slots
+// per segment.  The rows share the scan's slot buffer (the scan runs only when the followed table is not accepted),
+// so a segment divides a scan chunk and has the same 2 KiB per slot.
+#ifndef SBAM_FOLLOW_SEG_LOG2
+#define SBAM_FOLLOW_SEG_LOG2 18  // (the sweep: DESIGN.md, Measurement)
+#endif
+constexpr int kFollowSeg = 1 << SBAM_FOLLOW_SEG_LOG2;
+constexpr int kFollowSlots = kFollowSeg / (kScanChunk / kScanSlots);
+static_assert(kFollowSeg >= (128 << 10) && kScanChunk % kFollowSeg == 0, "a chain's exit lies in the next segment");
+enum : int32_t { FOLLOW_STOP = 1, FOLLOW_PARSE = 2, FOLLOW_OVERFLOW = 4, FOLLOW_NOENTRY = 8 };
+struct FollowSegs {  // per segment (sbam_layout.h: follow_segs)
+  int64_t *entry, *exit;  // where its chain began (-1: no entry found) and the first position it did not take
+  int32_t *rows, *kind;   // blocks on its chain (exact also past the slots); FOLLOW_* (0: left through its far edge)
+  int32_t *cnt;           // rows the accepted table takes from it
+  int64_t *off;           // their exclusive sums
+};
+inline int64_t follow_segments(int64_t D, int64_t start_rel) {
+  const int64_t n = (D + kFollowSeg - 1) / kFollowSeg - start_rel / kFollowSeg;
+  return n > 1 ? n : 1;
+}
+// follow + link + counts; verdict: two words (first unusable segment, first stopped segment; set here)
+hipError_t launch_follow_blocks(const uint8_t *d, int64_t D, int64_t start_rel, int64_t nseg, FollowSegs fs,
+                                Candidate *slots, int64_t *verdict, hipStream_t s);
+hipError_t launch_follow_compact(const Candidate *slots, FollowSegs fs, int64_t nseg, Candidate *out, hipStream_t s);
+// FindBlockStart without a candidate list, on the bytes themselves
+hipError_t launch_find_block_starts_bytes(const uint8_t *d, int64_t D, const int64_t *starts, int64_t n,
+                                          int32_t blocks_to_check, int64_t *out, hipStream_t s);
 hipError_t launch_scan_slots(const uint8_t *d, int64_t D, int32_t *chunk_counts, int64_t nchunks, Candidate *slots,
                              int64_t *overflow, hipStream_t s);
 hipError_t launch_scan_compact(const Candidate *slots, const int32_t *chunk_counts, const int64_t *chunk_offsets,

@@ -35,6 +35,12 @@ struct Carve {
   size_t at_ = 0;  // the end of the last column
 };
 
+// The followed block table's nseg segments, as R = FollowSegs
+template <class R>
+R follow_segs(Carve &k, size_t nseg) {
+  return R{k.i64(nseg), k.i64(nseg), k.i32(nseg), k.i32(nseg), k.i32(nseg), k.i64(nseg)};
+}
+
 // loadReads' n records, as R = RecordColumnsDev
 template <class R>
 R record_cols(Carve &k, size_t n) {

@@ -247,6 +247,8 @@ _SIGNATURES = {  # (restype, argtypes) of every symbol include/sbam.h declares
     "sbam_version": (ctypes.c_char_p, []),
     "sbam_find_block_starts": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "sbam_scan_blocks": (ctypes.c_int, [_vp, _P(_i64)]),
+    "sbam_scan_path": (ctypes.c_int, [_vp, _P(_i32), _P(_i32), _P(_i64)]),
+    "sbam_follow_segment_bytes": (ctypes.c_int, []),
     "sbam_get_blocks": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64]),
     "sbam_inflate": (ctypes.c_int, [_vp, _P(_i64)]),
     "sbam_inflate_fallbacks": (ctypes.c_int, [_vp, _P(_i64)]),
@@ -601,6 +603,13 @@ class BamFile:
         n = ctypes.c_int64(0)
         self._check(self.L.sbam_scan_blocks(self.ctx, ctypes.byref(n)))
         return n.value
+
+    def scan_path(self) -> dict:
+        """What the last block scan did (sbam_scan_path): `followed` the headers' BSIZE hops to the table, `fell_back`
+        to the byte scan after trying that; `segments` followed (0: not tried)."""
+        a, b, n = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0)
+        self._check(self.L.sbam_scan_path(self.ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(n)))
+        return {"followed": bool(a.value), "fell_back": bool(b.value), "segments": int(n.value)}
 
     def blocks(self):
         """(start, compressedSize, uncompressedSize, uncompressedOffset) arrays (IndexBlocks.scala:40-44)."""
