@@ -864,7 +864,7 @@ int sbam_find_block_starts(sbam_ctx *c, const int64_t *starts, int64_t n, int32_
   int64_t *d_q = c->d_qa, *d_o = c->d_qb;
   HIPCHK(c, hipMemcpyAsync(d_q, rel.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
   if (c->ncand >= 0)  // a candidate list exists: search it
-    HIPCHK(c, launch_find_block_starts(c->d_comp, c->D, c->d_cand, c->ncand, d_q, n, nchk, d_o, c->stream));
+    HIPCHK(c, launch_find_block_starts(c->D, c->d_cand, c->ncand, d_q, n, nchk, d_o, c->stream));
   else  // none (the table was followed, or nothing has run): the same rules on the bytes behind each start
     HIPCHK(c, launch_find_block_starts_bytes(c->d_comp, c->D, d_q, n, nchk, d_o, c->stream));
   HIPCHK(c, hipMemcpyAsync(out, d_o, n * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));

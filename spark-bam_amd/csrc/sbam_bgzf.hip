@@ -2,16 +2,13 @@
 //
 //  * BGZF block-header scan   (Header.make bgzf/.../block/Header.scala:48-83, MetadataStream.scala:23-54,
 //                              FindBlockStart.scala:8-36)
-//  * batched raw-DEFLATE inflate (Stream.scala:31-71; RFC 1951 semantics of java.util.zip.Inflater)
-//  The record-boundary checker and record chain live in sbam_check.hip.
+//  The inflate kernels live in sbam_inflate.hip, the record-boundary checker and record chain in sbam_check.hip.
 //
 // All byte/integer work: no MFMA (no dense contraction).  Design notes and rooflines: DESIGN.md.
 #include "sbam_device.h"
 #include "sbam_internal.h"
 
 namespace sbam {
-
-SB_DEV uint32_t brev(uint32_t code, int len) { return __builtin_bitreverse32(code) >> (32 - len); }
 
 // ================================================================================================
 // 1. BGZF header scan
@@ -40,28 +37,6 @@ SB_DEV void load32(const uint8_t *d, int64_t q0, uint32_t w[8]) {
   const uint4 b = *reinterpret_cast<const uint4 *>(d + q0 + 16);
   w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
   w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-}
-
-__global__ __launch_bounds__(kScanThreads) void k_scan_count(const uint8_t *__restrict__ d, int64_t D,
-                                                              int32_t *__restrict__ chunk_counts) {
-  const int64_t cbase = (int64_t)blockIdx.x * kScanChunk;
-  const int64_t cend = min(cbase + (int64_t)kScanChunk, D);
-  int cnt = 0;
-  for (int64_t it = cbase; it < cend; it += kScanStep) {
-    const int64_t q0 = it + threadIdx.x * 16;
-    if (q0 < cend) {
-      uint32_t w[8];
-      load32(d, q0, w);
-      uint32_t bits = header_bits16(w, q0, D);
-      if (q0 + 16 > cend) bits &= (1u << (cend - q0)) - 1u;
-      cnt += __popc(bits);
-    }
-  }
-  __shared__ int s[kScanThreads / 64];
-  for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-  if (lane_id() == 0) s[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) chunk_counts[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
 }
 
 SB_DEV void fill_candidate(const uint8_t *d, int64_t D, int64_t q, Candidate &c) {
@@ -127,7 +102,7 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_write(const uint8_t *__re
 // One-pass form (round 3): the candidates of chunk b written to its kScanSlots fixed slots, its count to
 // chunk_counts[b] (slots past kScanSlots are not written; *overflow is set and the caller runs k_scan_write with the
 // exact offsets instead), then k_scan_compact moves the slots into file order — the compressed bytes are read once
-// instead of twice (k_scan_count + k_scan_write).  Round 4: P positions per thread and iteration (P + 16 B loaded as
+// instead of twice (a count pass + k_scan_write).  Round 4: P positions per thread and iteration (P + 16 B loaded as
 // 16-B pieces, the next one's prefetched while this one's candidates are ranked), and one barrier per iteration
 // without candidates (an "any candidate" flag in three rotating LDS words: the one for iteration i + 1 is cleared
 // before iteration i's barrier, after every read of it in iteration i - 2).  Scan at 10 GB with P = 16 / 32 / 64:
@@ -504,11 +479,6 @@ __global__ __launch_bounds__(256) void k_find_block_starts_bytes(const uint8_t *
 // launch wrappers
 // ================================================================================================
 
-hipError_t launch_scan_count(const uint8_t *d, int64_t D, int32_t *cc, int64_t nchunks, hipStream_t s) {
-  if (nchunks == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_scan_count, dim3((unsigned)nchunks), dim3(kScanThreads), 0, s, d, D, cc);
-  return hipGetLastError();
-}
 hipError_t launch_scan_write(const uint8_t *d, int64_t D, const int64_t *off, int64_t nchunks, Candidate *c,
                              hipStream_t s) {
   if (nchunks == 0) return hipSuccess;
@@ -539,8 +509,8 @@ hipError_t launch_chain_verify(const Candidate *c, int64_t n, int64_t first, int
                      reinterpret_cast<unsigned long long *>(first_stop));
   return hipGetLastError();
 }
-hipError_t launch_find_block_starts(const uint8_t *, int64_t D, const Candidate *c, int64_t ncand, const int64_t *st,
-                                    int64_t n, int32_t nchk, int64_t *out, hipStream_t s) {
+hipError_t launch_find_block_starts(int64_t D, const Candidate *c, int64_t ncand, const int64_t *st, int64_t n,
+                                    int32_t nchk, int64_t *out, hipStream_t s) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_find_block_starts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c, ncand, D, st, n,
                      nchk, out);

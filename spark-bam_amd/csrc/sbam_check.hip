@@ -18,7 +18,6 @@
 // predicates are evaluated once per byte offset and shared by the four positions that read that int32, and flags,
 // keys and PASS0 bits are counted / formed on whole planes.
 #include <algorithm>
-#include <atomic>
 #include <type_traits>
 
 #include "sbam_device.h"
@@ -36,13 +35,12 @@ constexpr int kWin = kTile + kHalo;         // staged window (multiple of 16)
 constexpr int kOpcWords = kWin / 128 + 4;   // per residue class: one bit per 4 window bytes (+ pad)
 constexpr int kNameWords = kWin / 32 + 4;   // one bit per window byte (+ pad)
 constexpr int kLdsLens = 4096;              // contig lengths kept in LDS when n_ref fits
-// workgroups per CU the register budget is sized for (launch bounds): k_check over boundary tiles / interior tiles,
-// k_check_bits (6: a few constants spill, +7 GB scratch traffic, same time; round 4 with the LDS trimmed to 26.8 KB
-// so that 6 workgroups fit: 41.5 vs 41.2 ms — not latency-bound)
-constexpr int kCheckWgs = 4, kCheckWgsInt = 5, kCheckWgsBits = 5;
+// workgroups per CU the register budget is sized for (launch bounds): k_check, k_check_bits (6: a few constants
+// spill, +7 GB scratch traffic, same time; round 4 with the LDS trimmed to 26.8 KB so that 6 workgroups fit: 41.5 vs
+// 41.2 ms — not latency-bound)
+constexpr int kCheckWgs = 4, kCheckWgsBits = 5;
 constexpr int kFlushTiles = 7;              // 7 tiles x 32 positions per lane < 255 (8-bit planes / counters)
 static_assert(kWin % 16 == 0, "window");
-static_assert((kTile / (4 * kCheckThreads)) % 2 == 0, "groups pair up within a tile (add4_paired)");
 
 SB_DEV uint64_t shfl_xor64(uint64_t v, int m) {
   const uint32_t lo = __shfl_xor((int)(uint32_t)v, m, 64), hi = __shfl_xor((int)(uint32_t)(v >> 32), m, 64);
@@ -98,7 +96,7 @@ struct GlobalBytes {
 
 template <bool EAGER, class Bytes>
 SB_DEV uint32_t check_chain(const StreamView &sv, const Bytes &u, int64_t s, int64_t a, int k, int R) {
-  auto g_i32 = [&](const Bytes &b, int64_t x) -> int32_t {
+  auto le32 = [&](const Bytes &b, int64_t x) -> int32_t {
     return (int32_t)(b(x) | (b(x + 1) << 8) | (b(x + 2) << 16) | (b(x + 3) << 24));
   };
   for (;;) {
@@ -108,8 +106,8 @@ SB_DEV uint32_t check_chain(const StreamView &sv, const Bytes &u, int64_t s, int
       if (k > 0 && s == sv.L) return W_SUCC | ((uint32_t)k << 24);
       return 1u | ((uint32_t)k << 24);
     }
-    const int32_t bs = g_i32(u, a), ri = g_i32(u, a + 4), rp = g_i32(u, a + 8), bmn = g_i32(u, a + 12);
-    const int32_t fnc = g_i32(u, a + 16), ls = g_i32(u, a + 20), nri = g_i32(u, a + 24), nrp = g_i32(u, a + 28);
+    const int32_t bs = le32(u, a), ri = le32(u, a + 4), rp = le32(u, a + 8), bmn = le32(u, a + 12);
+    const int32_t fnc = le32(u, a + 16), ls = le32(u, a + 20), nri = le32(u, a + 24), nrp = le32(u, a + 28);
     const uint32_t K = (uint32_t)k << 24;
     uint32_t F = ref_err(ri, rp, nullptr, sv.lens, sv.nref) << 1;
     const int32_t lrn = bmn & 0xff;
@@ -321,8 +319,8 @@ __global__ __launch_bounds__(256) void k_p0_count(const unsigned long long *__re
   if (threadIdx.x == 0) chunk_cnt[blockIdx.x] = (int32_t)(s_c[0] + s_c[1] + s_c[2] + s_c[3]);
 }
 
-// The same counts from the record-0 pass's per-tile, per-wave counts (k_check_bits / k_check<MODE_COUNTS, 2>): a chunk
-// is 16 whole tiles, so its count is 64 integers instead of 16 KiB of bitmap.
+// The same counts from the record-0 pass's per-tile, per-wave counts (k_check_bits / k_check<MODE_COUNTS>): a chunk is
+// 16 whole tiles, so its count is 64 integers instead of 16 KiB of bitmap.
 __global__ __launch_bounds__(256) void k_p0_count_tiles(const int32_t *__restrict__ tile_pass0, int64_t ntiles,
                                                         int64_t nch, int32_t *__restrict__ chunk_cnt) {
   const int64_t ch = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -872,12 +870,10 @@ struct Planes {  // carry-save bit planes: per-flag counts of up to 255 values p
 // Count one checked position into the lane's accumulators (full-check Counts semantics).
 struct Acc {
   Planes pl;
-  Planes kp;         // interior tiles: one-hot key planes (bit k = a position with key k; bit 0 = PASS0, ignored)
   uint64_t keyc[3];  // 8-bit counters per key (8 per word)
   uint32_t n_succ, n_tff, n_halo;
   SB_DEV void clear() {
     pl.clear();
-    kp.clear();
     keyc[0] = keyc[1] = keyc[2] = 0;
     n_succ = n_tff = n_halo = 0;
   }
@@ -937,44 +933,6 @@ SB_DEV uint32_t classify_interior(uint32_t w, uint32_t *k12, uint32_t *pair, uin
   return F;
 }
 
-// Add a 4-plane number (weights 1, 2, 4, 8) into the planes.
-SB_DEV void add_planes4(Planes &pl, uint32_t o1, uint32_t o2, uint32_t o4, uint32_t o8) {
-  uint32_t c = pl.p[0] & o1;
-  pl.p[0] ^= o1;
-  const uint32_t o[3] = {o2, o4, o8};
-#pragma unroll
-  for (int j = 1; j <= 3; j++) {
-    const uint32_t x = pl.p[j] ^ o[j - 1];
-    const uint32_t cn = (pl.p[j] & o[j - 1]) | (c & x);
-    pl.p[j] = x ^ c;
-    c = cn;
-  }
-#pragma unroll
-  for (int j = 4; j < 8; j++) {
-    const uint32_t t = pl.p[j] & c;
-    pl.p[j] ^= c;
-    c = t;
-  }
-}
-// 4:3 compressor of four words into (ones, twos, fours); with a held (ones, twos, fours) from the previous group
-// the two are summed into a 4-plane number and added once (pairs of groups share one carry chain)
-SB_DEV void add4_paired(Planes &pl, const uint32_t v[4], uint32_t (&h)[3], bool second) {
-  const uint32_t x1a = v[0] ^ v[1], c1 = v[0] & v[1];
-  const uint32_t x2a = v[2] ^ v[3], c2 = v[2] & v[3];
-  const uint32_t o1 = x1a ^ x2a, c3 = x1a & x2a;
-  const uint32_t o2 = c1 ^ c2 ^ c3, o4 = (c1 & c2) | (c3 & (c1 ^ c2));
-  if (!second) {
-    h[0] = o1;
-    h[1] = o2;
-    h[2] = o4;
-    return;
-  }
-  const uint32_t s1 = h[0] ^ o1, k1 = h[0] & o1;
-  const uint32_t s2 = h[1] ^ o2 ^ k1, k2 = (h[1] & o2) | (k1 & (h[1] ^ o2));
-  const uint32_t s4 = h[2] ^ o4 ^ k2, k4 = (h[2] & o4) | (k2 & (h[2] ^ o4));
-  add_planes4(pl, s1, s2, s4, k4);
-}
-
 // 4:3 compressor of four bit-plane words into (ones, twos, fours) for Planes::add
 SB_DEV void add4(Planes &pl, const uint32_t v[4]) {
   const uint32_t x1a = v[0] ^ v[1], c1 = v[0] & v[1];
@@ -994,11 +952,7 @@ SB_DEV void flush_acc(Acc &acc, unsigned long long *s_acc, int lane) {
   }
 #pragma unroll
   for (int k = 0; k < 21; k++) {
-    uint32_t v = wave_sum((uint32_t)(acc.keyc[k >> 3] >> (8 * (k & 7))) & 0xffu);
-    if (k >= 1 && k <= 19) {
-#pragma unroll
-      for (int j = 0; j < 8; j++) v += (uint32_t)__popcll(__ballot((acc.kp.p[j] >> k) & 1u)) << j;
-    }
+    const uint32_t v = wave_sum((uint32_t)(acc.keyc[k >> 3] >> (8 * (k & 7))) & 0xffu);
     if (lane == 0 && v) atomicAdd(&s_acc[19 + k], (unsigned long long)v);
   }
   const uint32_t a = wave_sum(acc.n_succ), b = wave_sum(acc.n_tff), h = wave_sum(acc.n_halo);
@@ -1027,10 +981,11 @@ SB_DEV void bykey_count(uint32_t *s_cnt, int lane, bool counted, uint32_t key, u
   }
 }
 
-// PART 0: every tile of [x0, x1); PART 1: only the interior tiles [tlo, thi) (interior_tiles), compiled without
-// the boundary path so its register budget is its own; PART 2: every tile except [tlo, thi).
-template <int MODE, int PART>
-__global__ __launch_bounds__(kCheckThreads, PART == 1 ? kCheckWgsInt : kCheckWgs) void k_check(
+// Every tile of [x0, x1) except [tlo, thi), the interior tiles that k_check_bits / k_eager_wave take (tlo == thi:
+// every tile).  What is left for this kernel: the boundary tiles of both checkers, and whole ranges for the words,
+// the by-key counts (MODE_WORDS / MODE_BYKEY skip nothing: tlo and thi are not read) and R == 0.
+template <int MODE>
+__global__ __launch_bounds__(kCheckThreads, kCheckWgs) void k_check(
     StreamView sv, int64_t x0, int64_t x1, int R, CountsDev cd, unsigned long long *__restrict__ bitmap,
     uint32_t *__restrict__ words, int64_t tlo, int64_t thi) {
   constexpr bool EAGER = MODE == MODE_EAGER;
@@ -1064,10 +1019,11 @@ __global__ __launch_bounds__(kCheckThreads, PART == 1 ? kCheckWgsInt : kCheckWgs
   acc.clear();
   int since_flush = 0;
 
-  const int64_t nskip = PART == 2 ? thi - tlo : 0;
-  const int64_t tcount = PART == 1 ? thi - tlo : ntiles - nskip;
-  for (int64_t ti = blockIdx.x; ti < tcount; ti += gridDim.x) {
-    const int64_t t = PART == 1 ? tlo + ti : (ti >= tlo ? ti + nskip : ti);
+  // (the words and the by-key counts have no interior kernel: their skip range is empty at compile time, which
+  // keeps tlo / thi out of those kernels' scalar registers — DESIGN.md §Measurement, by-key + 0.7 % without it)
+  const int64_t nskip = (MODE == MODE_COUNTS || MODE == MODE_EAGER) ? thi - tlo : 0;
+  for (int64_t ti = blockIdx.x; ti < ntiles - nskip; ti += gridDim.x) {
+    const int64_t t = ti >= tlo ? ti + nskip : ti;
     const int64_t base = x0a + t * kTile;
     __syncthreads();
     stage_tile(sv, base, s_win, s_opc, s_nbad);
@@ -1077,9 +1033,8 @@ __global__ __launch_bounds__(kCheckThreads, PART == 1 ? kCheckWgsInt : kCheckWgs
     __syncthreads();
     const Tile tl{s_win, s_opc, s_nbad, base, s_nxt, s_pw[threadIdx.x >> 6]};
     const uint32_t *w32 = reinterpret_cast<const uint32_t *>(s_win);
-    uint32_t hkp[3] = {0, 0, 0}, hpl[3] = {0, 0, 0};  // held compressed counts of an even group (add4_paired)
-    constexpr bool TILECNT = MODE == MODE_COUNTS && PART == 2;  // boundary tiles of the bit-sliced pass
-    uint32_t tc = 0;                                             // PASS0 positions of the words this lane writes
+    constexpr bool TILECNT = MODE == MODE_COUNTS;  // the tiles k_check_bits leaves: between them, every tile's count
+    uint32_t tc = 0;                               // PASS0 positions of the words this lane writes
     auto run_tile = [&](auto interior_tag) {
     constexpr bool INTERIOR = decltype(interior_tag)::value;
 #pragma unroll 1
@@ -1125,45 +1080,21 @@ __global__ __launch_bounds__(kCheckThreads, PART == 1 ? kCheckWgsInt : kCheckWgs
       if (TILECNT && (lane & 15) == 0 && (INTERIOR || xg < x1)) tc += (uint32_t)__popcll(v);
       if (!COUNTS) continue;
       uint32_t Fo[4];
-      if constexpr (INTERIOR && !BYKEY) {
-        uint32_t oh[4];
-        bool low = false;
 #pragma unroll
-        for (int o = 0; o < 4; o++) {
-          Fo[o] = wd[o] & 0x7ffffu;
-          oh[o] = 1u << __popc(Fo[o]);
-          low |= (oh[o] & 6u) != 0;  // key 1 or 2
-        }
-        if (__ballot(low)) {
-#pragma unroll
-          for (int o = 0; o < 4; o++) {
-            uint32_t oh2;
-            if (oh[o] & 6u) classify_interior(wd[o], s_k12, s_pair, oh2);
-          }
-        }
-        add4_paired(acc.kp, oh, hkp, (j & 1) != 0);
-      } else {
-#pragma unroll
-        for (int o = 0; o < 4; o++) {
-          uint32_t key = 0;
-          bool counted = false;
-          Fo[o] = 0;
-          if (wd[o] != W_NONE && wd[o] != W_PASS0)
-            Fo[o] = acc.classify<BYKEY>(wd[o], cd, s_k12, s_pair, key, counted);
-          if (BYKEY) bykey_count(s_cnt, lane, counted, key, Fo[o]);
-        }
+      for (int o = 0; o < 4; o++) {
+        uint32_t key = 0;
+        bool counted = false;
+        Fo[o] = 0;
+        if (wd[o] != W_NONE && wd[o] != W_PASS0)
+          Fo[o] = acc.classify<BYKEY>(wd[o], cd, s_k12, s_pair, key, counted);
+        if (BYKEY) bykey_count(s_cnt, lane, counted, key, Fo[o]);
       }
-      if constexpr (INTERIOR && !BYKEY) add4_paired(acc.pl, Fo, hpl, (j & 1) != 0);
-      else add4(acc.pl, Fo);
+      add4(acc.pl, Fo);
     }
     };
-    if constexpr (PART == 1) {
+    if (base >= x0 && base + kTile <= x1 && base + kTile + kInteriorTail <= sv.L)
       run_tile(std::integral_constant<bool, true>{});
-    } else {
-      if (base >= x0 && base + kTile <= x1 && base + kTile + kInteriorTail <= sv.L)
-        run_tile(std::integral_constant<bool, true>{});
-      else run_tile(std::integral_constant<bool, false>{});
-    }
+    else run_tile(std::integral_constant<bool, false>{});
     if (TILECNT && cd.tile_pass0) {
       const uint32_t c = wave_sum(tc);
       if (lane == 0) cd.tile_pass0[t * 4 + (int)(threadIdx.x >> 6)] = (int32_t)c;
@@ -1197,7 +1128,7 @@ __global__ __launch_bounds__(kCheckThreads, PART == 1 ? kCheckWgsInt : kCheckWgs
 }
 
 // ---- full-check Counts over interior tiles, bit-sliced ------------------------------------------------------------
-// k_check<MODE_COUNTS, *> evaluates a position's 19 flags into one word and counts the words.  Here the positions
+// k_check<MODE_COUNTS> evaluates a position's 19 flags into one word and counts the words.  Here the positions
 // are the bits: lane t of the workgroup owns the 32 positions 1024 j + 4 t + o (j < 8, o < 4) of a tile, and every
 // per-position predicate becomes one bit of a per-lane "plane" (bit 31 - (4 j + o), appended by one v_addc:
 // plane + plane + the predicate's lane mask as carry-in).  Then
@@ -1611,8 +1542,8 @@ __global__ __launch_bounds__(kCheckThreads, kCheckWgsBits) void k_check_bits(Str
 // eager.Checker fails a position at its first failing check, and the first checks are the two reference indices
 // (refIdx, nextRefIdx in [-1, n_ref): PosChecker.scala:43-63, eager/Checker.scala:24-126).  So every position is
 // first tested on those two fields alone; only the survivors — true record starts and the few positions whose
-// indices happen to be small — are checked in full.  Same PASS0 bitmap as k_check<MODE_EAGER, 1>.
-// Round 5: no workgroup barrier (round 2-4's k_eager staged 8 KiB tiles per 256-thread workgroup, and its waves
+// indices happen to be small — are checked in full.  Same PASS0 bitmap as k_check<MODE_EAGER> writes for these tiles.
+// Round 5: no workgroup barrier (the kernel of rounds 2-4 staged 8 KiB tiles per 256-thread workgroup, and its waves
 // waited for one another at five barriers per tile and for one wave's survivor drain: 9.1 ms at 10 GB); every wave
 // streams its own tiles.  Lane l holds the 16-B pieces 1024 k + 16 l of the tile (k < 8; one coalesced 16-B load per piece) and
 // decides its 16 positions x = 1024 k + 16 l + j of each piece:
@@ -1897,30 +1828,8 @@ static void interior_tiles(const StreamView &sv, int64_t x0, int64_t x1, int64_t
   *thi = lim - x0a >= kTile ? (lim - x0a) / kTile : 0;
   if (*thi < *tlo) *thi = *tlo;
 }
-// Grid of the grid-stride k_check<MODE, PART> launch: at least the workgroups resident on the whole device.
-template <int MODE, int PART>
-static int resident_grid(int64_t ntiles) {
-  static std::atomic<int> cached[16];
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  int g = cached[dev & 15].load(std::memory_order_relaxed);
-  if (g <= 0) {
-    int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_check<MODE, PART>, kCheckThreads, 0) != hipSuccess ||
-        per_cu < 1)
-      per_cu = 1;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-    g = per_cu * cus;
-    cached[dev & 15].store(g, std::memory_order_relaxed);
-  }
-  // many more workgroups than slots, ~40 tiles each: tile costs differ (data, counter flushes), and a slot that
-  // finishes early takes the next workgroup (measured at 10 GB: 1280 → 121 ms, 2048 → 114, 81920 → 99)
-  const int64_t want = std::max<int64_t>(g, std::min<int64_t>(ntiles / 40, 131072));
-  return (int)(ntiles < 1 ? 1 : ntiles < want ? ntiles : want);
-}
-
-// Grid of k_check_bits over ntiles interior tiles (same policy as resident_grid; the occupancy depends on the
-// dynamic LDS of the contig lengths).
+// Grid of the grid-stride k_check_bits launch over ntiles interior tiles: at least the workgroups resident on the
+// whole device (the occupancy depends on the dynamic LDS of the contig lengths).
 static int bits_grid(int64_t ntiles, size_t shmem) {
   int per_cu = 0, cus = 0, dev = 0;
   (void)hipGetDevice(&dev);
@@ -1928,22 +1837,10 @@ static int bits_grid(int64_t ntiles, size_t shmem) {
       per_cu < 1)
     per_cu = 1;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+  // many more workgroups than slots, ~40 tiles each: tile costs differ (data, counter flushes), and a slot that
+  // finishes early takes the next workgroup (measured at 10 GB: 1280 → 121 ms, 2048 → 114, 81920 → 99)
   const int64_t want = std::max<int64_t>((int64_t)per_cu * cus, std::min<int64_t>(ntiles / 40, 131072));
   return (int)(ntiles < 1 ? 1 : ntiles < want ? ntiles : want);
-}
-// Record-0 pass of mode MODE over [x0, x1): interior tiles by k_check<MODE, 1>, the rest by k_check<MODE, 2>.
-template <int MODE>
-static void launch_split_check(StreamView sv, int64_t x0, int64_t x1, int32_t R, CountsDev cd,
-                               unsigned long long *bitmap, hipStream_t s) {
-  int64_t tlo, thi;
-  interior_tiles(sv, x0, x1, &tlo, &thi);
-  const int64_t nt = ntiles_of(x0, x1), ni = thi - tlo;
-  if (ni > 0)
-    hipLaunchKernelGGL((k_check<MODE, 1>), dim3(resident_grid<MODE, 1>(ni)), dim3(kCheckThreads), 0, s, sv, x0, x1, R,
-                       cd, bitmap, nullptr, tlo, thi);
-  if (nt > ni)
-    hipLaunchKernelGGL((k_check<MODE, 2>), dim3(check_grid(nt - ni)), dim3(kCheckThreads), 0, s, sv, x0, x1, R, cd,
-                       bitmap, nullptr, tlo, thi);
 }
 static int chain_grid(int64_t x0, int64_t x1) {
   const int64_t words = (x1 - (x0 & ~(int64_t)63) + 63) >> 6;
@@ -1957,27 +1854,25 @@ hipError_t launch_check_full_counts(StreamView sv, int64_t x0, int64_t x1, int32
   *tiles_counted = false;
   if (x1 <= x0) return hipSuccess;
   if (by_key) {
-    hipLaunchKernelGGL((k_check<MODE_BYKEY, 0>), dim3(check_grid(ntiles_of(x0, x1))), dim3(kCheckThreads), 0, s, sv,
-                       x0, x1, R, cd, bitmap, nullptr, (int64_t)0, (int64_t)0);
-  } else if (R > 0) {
-    // interior tiles bit-sliced (k_check_bits), the boundary tiles by k_check<MODE_COUNTS, 2>; between them every
-    // tile's PASS0 count when cd.tile_pass0 is set
-    *tiles_counted = cd.tile_pass0 != nullptr;
-    int64_t tlo, thi;
-    interior_tiles(sv, x0, x1, &tlo, &thi);
-    const int64_t nt = ntiles_of(x0, x1), ni = thi - tlo;
-    if (ni > 0) {
-      const size_t shmem = (sv.nref <= kLdsLens ? (size_t)sv.nref + 1 : 1) * sizeof(int32_t);
-      hipLaunchKernelGGL(k_check_bits, dim3(bits_grid(ni, shmem)), dim3(kCheckThreads), shmem, s, sv, x0, R, cd,
-                         bitmap, tlo, thi);
-    }
-    if (nt > ni)
-      hipLaunchKernelGGL((k_check<MODE_COUNTS, 2>), dim3(check_grid(nt - ni)), dim3(kCheckThreads), 0, s, sv, x0, x1,
-                         R, cd, bitmap, nullptr, tlo, thi);
-  } else {  // Success(0) everywhere, or contig lengths past the LDS table: the general pass
-    hipLaunchKernelGGL((k_check<MODE_COUNTS, 0>), dim3(check_grid(ntiles_of(x0, x1))), dim3(kCheckThreads), 0, s, sv,
-                       x0, x1, R, cd, bitmap, nullptr, (int64_t)0, (int64_t)0);
+    hipLaunchKernelGGL((k_check<MODE_BYKEY>), dim3(check_grid(ntiles_of(x0, x1))), dim3(kCheckThreads), 0, s, sv, x0,
+                       x1, R, cd, bitmap, nullptr, (int64_t)0, (int64_t)0);
+    return hipGetLastError();
   }
+  // interior tiles bit-sliced (k_check_bits), the rest by k_check<MODE_COUNTS>; between them every tile's PASS0 count
+  // when cd.tile_pass0 is set
+  *tiles_counted = cd.tile_pass0 != nullptr;
+  int64_t tlo, thi;
+  interior_tiles(sv, x0, x1, &tlo, &thi);
+  if (R == 0) thi = tlo;  // Success(0) everywhere: every position is PASS0, no tile for the bit-sliced pass
+  const int64_t nt = ntiles_of(x0, x1), ni = thi - tlo;
+  if (ni > 0) {
+    const size_t shmem = (sv.nref <= kLdsLens ? (size_t)sv.nref + 1 : 1) * sizeof(int32_t);
+    hipLaunchKernelGGL(k_check_bits, dim3(bits_grid(ni, shmem)), dim3(kCheckThreads), shmem, s, sv, x0, R, cd, bitmap,
+                       tlo, thi);
+  }
+  if (nt > ni)
+    hipLaunchKernelGGL((k_check<MODE_COUNTS>), dim3(check_grid(nt - ni)), dim3(kCheckThreads), 0, s, sv, x0, x1, R, cd,
+                       bitmap, nullptr, tlo, thi);
   return hipGetLastError();
 }
 hipError_t launch_check_full_chains(StreamView sv, int64_t x0, int64_t x1, int32_t R, int32_t by_key, CountsDev cd,
@@ -2022,27 +1917,24 @@ hipError_t launch_chain_list_run(StreamView sv, int64_t x0, int64_t x1, int32_t 
 hipError_t launch_check_eager_pass0(StreamView sv, int64_t x0, int64_t x1, int32_t R, unsigned long long *bitmap,
                                     hipStream_t s) {
   if (x1 <= x0) return hipSuccess;
-  if (R == 0) {  // Success(0) everywhere: no prefilter
-    launch_split_check<MODE_EAGER>(sv, x0, x1, R, CountsDev{}, bitmap, s);
-    return hipGetLastError();
-  }
   int64_t tlo, thi;
   interior_tiles(sv, x0, x1, &tlo, &thi);
+  if (R == 0) thi = tlo;  // Success(0) everywhere: no prefilter, no tile for k_eager_wave
   const int64_t nt = ntiles_of(x0, x1), ni = thi - tlo;
   if (ni > 0) {  // ~10 tiles per wave: a wave that finishes early takes the next workgroup
     const int64_t g = std::max<int64_t>(1, std::min<int64_t>((ni + 10 * kEwWaves - 1) / (10 * kEwWaves), 131072));
     hipLaunchKernelGGL(k_eager_wave, dim3((unsigned)g), dim3(64 * kEwWaves), 0, s, sv, x0, (int)R, bitmap, tlo, thi);
   }
   if (nt > ni)
-    hipLaunchKernelGGL((k_check<MODE_EAGER, 2>), dim3(check_grid(nt - ni)), dim3(kCheckThreads), 0, s, sv, x0, x1, R,
+    hipLaunchKernelGGL((k_check<MODE_EAGER>), dim3(check_grid(nt - ni)), dim3(kCheckThreads), 0, s, sv, x0, x1, R,
                        CountsDev{}, bitmap, nullptr, tlo, thi);
   return hipGetLastError();
 }
 hipError_t launch_check_words(StreamView sv, int64_t x0, int64_t x1, int32_t R, uint32_t *words,
                               unsigned long long *bitmap, hipStream_t s) {
   if (x1 <= x0) return hipSuccess;
-  hipLaunchKernelGGL((k_check<MODE_WORDS, 0>), dim3(check_grid(ntiles_of(x0, x1))), dim3(kCheckThreads), 0, s, sv, x0,
-                     x1, R, CountsDev{}, bitmap, words, (int64_t)0, (int64_t)0);
+  hipLaunchKernelGGL((k_check<MODE_WORDS>), dim3(check_grid(ntiles_of(x0, x1))), dim3(kCheckThreads), 0, s, sv, x0, x1,
+                     R, CountsDev{}, bitmap, words, (int64_t)0, (int64_t)0);
   hipLaunchKernelGGL(k_chains, dim3(chain_grid(x0, x1)), dim3(256), 0, s, sv, x0, x1, R, bitmap, CountsDev{}, 0, words);
   return hipGetLastError();
 }

@@ -1,4 +1,4 @@
-// sbam_internal.h — launch wrappers shared by the kernels (sbam_kernels.hip) and the C-ABI host
+// sbam_internal.h — launch wrappers shared by the kernels (sbam_*.hip) and the C-ABI host
 // layer (sbam_api.cpp).  Not part of the public ABI (include/sbam.h is).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -56,8 +56,8 @@ struct CountsDev {  // mirrors sbam_counts (int64 fields) in device memory
   unsigned long long *pair;  // [19][19]
   unsigned long long *scalars;  // n_positions, n_success, n_too_few_fixed, n_halo
   unsigned long long *totals;   // [19] per-flag totals over every counted position
-  // [ntiles][4]: the record-0 pass's PASS0 positions per tile and wave (set only for the bit-sliced pass, which then
-  // writes every tile's; the chain pass's chunk counts come from these instead of a second read of the bitmap)
+  // [ntiles][4]: the record-0 pass's PASS0 positions per tile and wave (set only for the full counts that are not
+  // by-key, which then write every tile's; the chain pass's chunk counts come from these instead of a second read of the bitmap)
   int32_t *tile_pass0 = nullptr;
 };
 
@@ -109,9 +109,8 @@ hipError_t launch_scan_write(const uint8_t *d, int64_t D, const int64_t *chunk_o
                              Candidate *cands, hipStream_t s);
 hipError_t launch_chain_verify(const Candidate *cands, int64_t ncand, int64_t first, int64_t D, int64_t *first_stop,
                                hipStream_t s);
-hipError_t launch_find_block_starts(const uint8_t *d, int64_t D, const Candidate *cands, int64_t ncand,
-                                    const int64_t *starts, int64_t n, int32_t blocks_to_check, int64_t *out,
-                                    hipStream_t s);
+hipError_t launch_find_block_starts(int64_t D, const Candidate *cands, int64_t ncand, const int64_t *starts, int64_t n,
+                                    int32_t blocks_to_check, int64_t *out, hipStream_t s);
 // (+ uoff[0..n]: the uncompressed offsets, computed on the device; wsum: (n + 255) / 256 int64 of scratch)
 hipError_t launch_gather_blocks(const Candidate *cands, int64_t first, int64_t n, int64_t *start, int32_t *hsize,
                                 int32_t *csize, int32_t *usize, int64_t *wsum, int64_t *uoff, hipStream_t s);
@@ -149,7 +148,7 @@ hipError_t launch_block_crc(const uint8_t *comp, int64_t D, const uint8_t *u, in
                             int64_t b1, uint32_t *crc, uint32_t *stored, unsigned long long *n_bad,
                             unsigned long long *first_bad, hipStream_t s);
 // Bitmaps cover [x0 & ~63, x1): bit (x - (x0 & ~63)) = call at x (0 for x < x0).
-// *tiles_counted: whether cd.tile_pass0 now holds every tile's PASS0 count (the bit-sliced pass ran)
+// *tiles_counted: whether cd.tile_pass0 now holds every tile's PASS0 count (it is set, and the run is not by-key)
 hipError_t launch_check_full_counts(StreamView sv, int64_t x0, int64_t x1, int32_t R, int32_t by_key, CountsDev cd,
                                     unsigned long long *bitmap, hipStream_t s, bool *tiles_counted);
 int64_t check_tiles(int64_t x0, int64_t x1);  // record-0 pass tiles of [x0, x1)

@@ -52,7 +52,7 @@ def test_synthetic_every_offset_and_counts(synth_file):
 @pytest.mark.parametrize("case", ["many_contigs", "many_contigs_short", "reads_to_check_0"])
 def test_counts_general_paths(synth_file, case):
     """Past the bit-sliced interior pass's LDS table of contig lengths (n_ref > 4096: the rare length probes read the
-    device table, round 5) and with reads_to_check = 0 (the general k_check<MODE_COUNTS, 0> over every tile), against
+    device table, round 5) and with reads_to_check = 0 (the general k_check<MODE_COUNTS> over every tile), against
     the oracle: 5000 contigs (the 84 real ones, then 4916 more, so refIdx values up to 4999 become in-range; "short":
     lengths 1-999, so refPos > length fires on many of them) and R = 0."""
     import sbam
