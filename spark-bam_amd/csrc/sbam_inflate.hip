@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "sbam_internal.h"
+#include "sbam_resolve_core.h"
 
 namespace sbam {
 
@@ -1081,7 +1082,7 @@ extern "C" int sbam_debug_wave_stats(unsigned long long *out, int reset) {
 #define WMARK(slot) do {} while (0)
 #define WADD(slot, v) do {} while (0)
 #endif
-#ifdef SBAM_WAVE_STATS  // resolver phases: slot 32 + k (RMARK), 39 = steps
+#ifdef SBAM_WAVE_STATS  // resolver phases: slot 32 + k (RMARK, k < 7), 39 = steps
 #define RMARK(k) do { const uint64_t t_ = __builtin_amdgcn_s_memtime(); rs_[k] += t_ - rt_; rt_ = t_; } while (0)
 #else
 #define RMARK(k) do {} while (0)
@@ -1826,10 +1827,14 @@ __global__ __launch_bounds__(64) void k_inflate_stored(const uint8_t *__restrict
 //      would start kSpan or more bytes after the chunk's base, and at the block's end);
 //   2. the ring dwords the chunk will write are zeroed, then literal bytes are written by byte stores and match
 //      bytes by LDS ORs of their (masked, shifted) dwords — lanes writing neighbouring bytes of one dword never race;
-//   3. literal words are written at once; matches go in rounds: a match is ready when its source ends at or before
-//      the first pending match of the chunk (the first pending one always is), ready matches copy in steps of up
-//      to 16 bytes (an overlapping copy doubles its distance per step) from the ring (distance <= kNear) or, for
-//      far sources, from the output already flushed to HBM;
+//   3. literal words are written at once; matches go in two passes.  Independents (the source ends at or before
+//      the chunk's base: nearly all) copy in steps of up to 16 bytes (an overlapping copy doubles its distance per
+//      step) from the ring (distance <= kNear) or, for far sources, from the output already flushed to HBM.
+//      Dependents (the source reaches into this chunk: about 3 matches and 26 bytes per step) are laid out one
+//      output byte per lane; each lane follows its byte's source back through the dependents in one descending
+//      sweep and copies the byte it ends at (sbam_resolve_core.h).  (Through round 6 matches went in dependency
+//      rounds, each with a cross-lane ready test and a copy loop as long as its slowest lane's: 2.43 rounds per
+//      step, 1.44 of them for those 3 matches.)
 //   4. completed output leaves in 1 KiB groups of 16-B aligned stores; a block's partial first and last 16-B chunks
 //      (shared with its neighbours) leave as byte stores.
 // A block's LZ77 window never leaves the chip except for the far copies; HBM sees the words once and the output
@@ -1841,6 +1846,7 @@ namespace rs {
 constexpr int kSpan = 1024;   // a chunk's words start within kSpan bytes of its base
 constexpr int kFlush = 1024;  // output bytes per group store (64 lanes x 16 B)
 }  // namespace rs
+namespace rc = sbam_resolve;
 
 template <int RB>
 struct RingGeom {
@@ -1994,96 +2000,147 @@ __global__ __launch_bounds__(64) void k_inflate_resolve(BlockTable bt, uint8_t *
     const bool mt = Le > 0;
     const bool far = d > G::kNear;
     const int srcEnd = mO - d + min(Le, d);
-    // far sources (already in HBM, final) are loaded now, 32 B ahead; their copies wait until a near copy needs
-    // them (the first pending match is far), so the loads overlap the near rounds
+    // far sources (already in HBM, final) are loaded now, 32 B ahead; the dependents' layout below runs while they
+    // are on their way
     u32x4 pf0 = {0u, 0u, 0u, 0u}, pf1 = {0u, 0u, 0u, 0u};
     if (mt && far) {
       pf0 = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(ob + mO - d));
       if (Le > 16) pf1 = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(ob + mO - d + 16));
     }
     // the next step's tokens, loaded after the far sources: a wait for a far source need not wait for them
-    // (as raw registers, split only after the rounds: see the end of the step)
+    // (as raw registers, split only after the matches: see the end of the step)
     uint32_t w2, n2;
     __builtin_memcpy(&w2, tk + tp2 + 2 * lane, 4);
     n2 = tk[tp2 + 2 * lane + 2];
     RMARK(3);  // match setup, far prefetch, next tokens issued
-    uint64_t pend = __ballot(mt);
-    const uint64_t below = (1ull << lane) - 1ull;
-    const int mEnd = mO + Le;
-    while (pend) {
-      const int f = __ffsll((unsigned long long)pend) - 1;
-      const int fr = __builtin_amdgcn_readlane(mO, f);
-      // ready: the source ends before the first pending output, or every pending output before this lane's ends
-      // at or before the source starts (pending outputs are disjoint and in lane order, so the nearest one decides)
-      const uint64_t pb = pend & below;
-      const int jn = pb ? 63 - __clzll((long long)pb) : lane;
-      const int endj = __shfl(mEnd, jn);
-      uint64_t ready = pend & __ballot(srcEnd <= fr || pb == 0 || endj <= mO - d);
-      if ((ready >> lane) & 1ull) {
-        int done = 0, deff = d;
-        while (done < Le) {
+    // ---- 3b / 3c. A match is independent when its source ends at or before the chunk's base: it is output of
+    // earlier steps and final.  A lane-local test, no rounds.  (Every far match is one: its source ends below
+    // mO - kNear + 258 < B.)  The rest are dependents: the source reaches into this chunk, a few short matches per
+    // step.  They go one output byte per lane, 64 bytes per batch; a dependent has mO - d > B - 258, so every source
+    // position below stays inside the ring (never far, never HBM).  Each lane follows its byte's source out of the
+    // dependents' outputs (sbam_resolve_core.h): what it then reads is a literal, an independent's byte or earlier
+    // output.  No lane reads a byte this pass writes, so the batches need no order among themselves.
+    static_assert(G::kNear > rc::kMaxMatch, "a dependent's source is near");
+    const bool ind = mt && srcEnd <= B;
+    const uint64_t dm = __ballot(mt && !ind);
+    // Batches and dependents both go last to first, so one loop does both jobs for a dependent k: bytes handed out
+    // earlier in the batch (they belong to later dependents) hop out of k's output, then k's own bytes take lanes
+    // [t, t + n) with their collapsed source.  A batch that fills up keeps visiting the earlier dependents for the hops.
+    uint64_t rem = dm;  // dependents with bytes still to hand out
+    int cut = 0;        // bytes of rem's last dependent that earlier batches took (from its end)
+    int dsrc = 0, ddst = -1;  // this lane's byte of the batch: where its value is, where it goes (< 0: no byte)
+    auto lay_out = [&]() {
+      int s = -(1 << 30), o = -1;  // (no byte yet: s hits nothing)
+      int t = 0, c = cut;
+      cut = 0;
+      uint64_t m = rem;
+      do {
+        const int k = 63 - __clzll((long long)m);
+        const uint64_t bit = 1ull << k;
+        m &= ~bit;
+        const int mk = __builtin_amdgcn_readlane(mO, k), dk = __builtin_amdgcn_readlane(d, k),
+                  lk = __builtin_amdgcn_readlane(Le, k);
+        const int r = s - mk;  // the hop: s in [mk, mk + lk)
+        const bool hit = rc::hop_hits(s, mk, lk);
+        const int left = lk - c, n = min(left, 64 - t);  // (n = 0 once the batch is full)
+        const int jj = lane - t + (left - n);            // the last n of the bytes left
+        const bool act = (uint32_t)(lane - t) < (uint32_t)n;
+        int rf = r, jf = jj;
+        if (lk > dk) {  // a self-overlapping run: offsets past its first period fold back (rare: the division)
+          int dv = dk;
+          asm volatile("" : "+v"(dv));
+          rf = rc::period_offset(r, dv);
+          jf = rc::period_offset(jj, dv);
+        }
+        const int base = mk - dk;
+        s = act ? base + jf : hit ? base + rf : s;
+        o = act ? mk + jj : o;
+        if (n == left) rem &= ~bit;
+        else if (t < 64) cut = c + n;  // the rest of k goes to the next batch
+        t += n;
+        c = 0;
+      } while (m);
+      dsrc = s;
+      ddst = o;
+    };
+    // the first batch is laid out here, ahead of the copies: it is register work only, and runs while the far
+    // sources and the next tokens are on their way
+    if (rem) lay_out();
+    // ---- 3b. independents: the existing copy loop, once
+    if (ind) {
+      int done = 0, deff = d;
+      while (done < Le) {
 #ifdef SBAM_WAVE_STATS
-          it_++;
+        it_++;
 #endif
-          const int n = min(min(Le - done, 16), deff);
-          const int src = mO + done - deff;
-          // the keep-mask of the first n bytes, read before the source (it was read after, a second LDS round trip
-          // on every iteration's dependent chain)
-          const uint4 km = *reinterpret_cast<const uint4 *>(s_keep + 4 * n);
-          uint32_t v0, v1, v2, v3;
-          if (far) {  // below the flushed mark: unaligned 16-B loads, past this CU's L1 (nt)
-            // each path waits for its own source here (the prefetched ones: vmcnt(2), the next step's two token
-            // loads may stay in flight): merged with the near path's registers, the compiler waited with vmcnt(0)
-            // after the join, so every near copy also waited for the next step's tokens
-            if (done >= 32) {
-              const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(ob + src));
-              v0 = x.x; v1 = x.y; v2 = x.z; v3 = x.w;
-              asm volatile("" : "+v"(v0), "+v"(v1), "+v"(v2), "+v"(v3));
-            } else {
-              const u32x4 x = done == 0 ? pf0 : pf1;
-              v0 = x.x; v1 = x.y; v2 = x.z; v3 = x.w;
-              asm volatile("" : "+v"(v0), "+v"(v1), "+v"(v2), "+v"(v3));
-            }
+        const int n = min(min(Le - done, 16), deff);
+        const int src = mO + done - deff;
+        // the keep-mask of the first n bytes, read before the source (it was read after, a second LDS round trip
+        // on every iteration's dependent chain)
+        const uint4 km = *reinterpret_cast<const uint4 *>(s_keep + 4 * n);
+        uint32_t v0, v1, v2, v3;
+        if (far) {  // below the flushed mark: unaligned 16-B loads, past this CU's L1 (nt)
+          // each path waits for its own source here (the prefetched ones: vmcnt(2), the next step's two token
+          // loads may stay in flight): merged with the near path's registers, the compiler waited with vmcnt(0)
+          // after the join, so every near copy also waited for the next step's tokens
+          if (done >= 32) {
+            const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(ob + src));
+            v0 = x.x; v1 = x.y; v2 = x.z; v3 = x.w;
+            asm volatile("" : "+v"(v0), "+v"(v1), "+v"(v2), "+v"(v3));
           } else {
-            const uint32_t xs = (Gr + (uint32_t)src) & G::kMask, qs = xs >> 2, ss = xs & 3u;
-            const uint32_t *p = ring + qs;  // (qs + 4 < kDw + kMirror: the mirror covers the wrap)
-            const uint32_t s0 = p[0], s1 = p[1], s2 = p[2], s3 = p[3], s4 = p[4];
-            v0 = __builtin_amdgcn_alignbyte(s1, s0, ss);
-            v1 = __builtin_amdgcn_alignbyte(s2, s1, ss);
-            v2 = __builtin_amdgcn_alignbyte(s3, s2, ss);
-            v3 = __builtin_amdgcn_alignbyte(s4, s3, ss);
+            const u32x4 x = done == 0 ? pf0 : pf1;
+            v0 = x.x; v1 = x.y; v2 = x.z; v3 = x.w;
+            asm volatile("" : "+v"(v0), "+v"(v1), "+v"(v2), "+v"(v3));
           }
-          // keep the first n bytes
-          v0 &= km.x;
-          v1 &= km.y;
-          v2 &= km.z;
-          v3 &= km.w;
-          // shift to the destination's byte offset and OR in
-          const uint32_t xd = (Gr + (uint32_t)(mO + done)) & G::kMask, qd = xd >> 2, s8 = (xd & 3u) * 8u;
-          const uint64_t a01 = ((uint64_t)v1 << 32 | v0) << s8, a12 = ((uint64_t)v2 << 32 | v1) << s8,
-                         a23 = ((uint64_t)v3 << 32 | v2) << s8, a34 = (uint64_t)v3 << s8;
-          ring_or5<G>(ring, qd, (uint32_t)a01, (uint32_t)(a01 >> 32), (uint32_t)(a12 >> 32), (uint32_t)(a23 >> 32),
-                      (uint32_t)(a34 >> 32));
-          done += n;
-          if (n == deff && deff < 16) deff *= 2;  // the copied bytes extend the period: 2·deff is a valid distance
+        } else {
+          const uint32_t xs = (Gr + (uint32_t)src) & G::kMask, qs = xs >> 2, ss = xs & 3u;
+          const uint32_t *p = ring + qs;  // (qs + 4 < kDw + kMirror: the mirror covers the wrap)
+          const uint32_t s0 = p[0], s1 = p[1], s2 = p[2], s3 = p[3], s4 = p[4];
+          v0 = __builtin_amdgcn_alignbyte(s1, s0, ss);
+          v1 = __builtin_amdgcn_alignbyte(s2, s1, ss);
+          v2 = __builtin_amdgcn_alignbyte(s3, s2, ss);
+          v3 = __builtin_amdgcn_alignbyte(s4, s3, ss);
         }
+        // keep the first n bytes
+        v0 &= km.x;
+        v1 &= km.y;
+        v2 &= km.z;
+        v3 &= km.w;
+        // shift to the destination's byte offset and OR in
+        const uint32_t xd = (Gr + (uint32_t)(mO + done)) & G::kMask, qd = xd >> 2, s8 = (xd & 3u) * 8u;
+        const uint64_t a01 = ((uint64_t)v1 << 32 | v0) << s8, a12 = ((uint64_t)v2 << 32 | v1) << s8,
+                       a23 = ((uint64_t)v3 << 32 | v2) << s8, a34 = (uint64_t)v3 << s8;
+        ring_or5<G>(ring, qd, (uint32_t)a01, (uint32_t)(a01 >> 32), (uint32_t)(a12 >> 32), (uint32_t)(a23 >> 32),
+                    (uint32_t)(a34 >> 32));
+        done += n;
+        if (n == deff && deff < 16) deff *= 2;  // the copied bytes extend the period: 2·deff is a valid distance
       }
-      pend &= ~ready;
-#ifdef SBAM_WAVE_STATS
-      rs_[7]++;  // rounds
-      {  // copy iterations: the wave's (the slowest lane's) and the sum over lanes
-        uint32_t mx = it_, sm = it_;
-        for (int o = 32; o >= 1; o >>= 1) {
-          mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
-          sm += (uint32_t)__shfl_xor((int)sm, o);
-        }
-        itw_ += mx;
-        itl_ += sm;
-        it_ = 0;
-      }
-#endif
     }
-    RMARK(4);  // rounds
+#ifdef SBAM_WAVE_STATS
+    {  // copy iterations: the wave's (the slowest lane's) and the sum over lanes
+      uint32_t mx = it_, sm = it_;
+      for (int o = 32; o >= 1; o >>= 1) {
+        mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
+        sm += (uint32_t)__shfl_xor((int)sm, o);
+      }
+      itw_ += mx;
+      itl_ += sm;
+      it_ = 0;
+    }
+#endif
+    RMARK(4);  // independents
+    // ---- 3c. dependents, second half: the bytes move (the first batch was laid out above; 3.3 % of steps have more)
+    for (;;) {
+      if (ddst >= 0) {
+        const uint8_t v = ring8[(Gr + (uint32_t)dsrc) & G::kMask];
+        const uint32_t x = (Gr + (uint32_t)ddst) & G::kMask;
+        ring8[x] = v;
+        if (x < 4u * G::kMirror) ring8[G::kRing + x] = v;
+      }
+      if (!rem) break;
+      lay_out();
+    }
+    RMARK(5);  // dependents
     B = E;
     // the wait for the next step's tokens, here: the compiler otherwise split them right after the loads (waiting
     // there), or let this step's last use of tn wait after the stores (one in-order vmcnt)
@@ -2091,9 +2148,9 @@ __global__ __launch_bounds__(64) void k_inflate_resolve(BlockTable bt, uint8_t *
     ta = w2 & 0xffffu;
     tb = w2 >> 16;
     tn = n2;
-    RMARK(5);  // the wait for the next tokens
+    RMARK(6);  // the wait for the next tokens
 #ifdef SBAM_WAVE_STATS
-    rs_[6]++;  // steps
+    rs_[7]++;  // steps
 #endif
     tp = tp2;
   }
@@ -2109,12 +2166,11 @@ __global__ __launch_bounds__(64) void k_inflate_resolve(BlockTable bt, uint8_t *
   }
   if (__ballot(toofar) != 0 && lane == 0 && redo) redo[atomicAdd(nredo, 1u)] = (int32_t)b;
 #ifdef SBAM_WAVE_STATS
-  // slots 32..37: phases (the tail in 37 with the total's remainder), 38: steps, 39: rounds
+  // slots 32..38: phases (the tail with the total's remainder), 39: steps; 29 / 30: the independents' copy
+  // iterations (the wave's, the sum over lanes)
   const uint64_t tot_ = __builtin_amdgcn_s_memtime() - rt0_;
   if (lane == 0) {
-    for (int i = 0; i < 6; i++) atomicAdd(&g_wave_stats[32 + i], (unsigned long long)rs_[i]);
-    atomicAdd(&g_wave_stats[38], (unsigned long long)rs_[6]);
-    atomicAdd(&g_wave_stats[39], (unsigned long long)rs_[7]);
+    for (int i = 0; i < 8; i++) atomicAdd(&g_wave_stats[32 + i], (unsigned long long)rs_[i]);
     atomicAdd(&g_wave_stats[31], (unsigned long long)tot_);
     atomicAdd(&g_wave_stats[29], (unsigned long long)itw_);
     atomicAdd(&g_wave_stats[30], (unsigned long long)itl_);

@@ -2,8 +2,12 @@
 """Python model of k_inflate_resolve's step structure (sbam_inflate.hip) over the synthetic BAM's token streams:
 128 tokens per step (two per lane), the step cut kSpan bytes past its base, matches in dependency rounds, copies in
 steps of <= 16 bytes with the overlapping-copy distance doubling.  Reports rounds and copy iterations per step (the
-wave pays the slowest ready lane of a round) under the kernel's readiness rule and under the exact rule (a match is
-ready when its source meets no pending output), so a change to either is priced before it is built.
+wave pays the slowest ready lane of a round) under the readiness rule the kernel had through round 6 and under the
+exact rule (a match is ready when its source meets no pending output), split into the first round and all later ones,
+and the two-pass scheme the kernel has now: independents (source ends at or before the step's base; also under the
+wider test, at or before the step's first match) in one copy loop, dependents one output byte per lane in batches
+of 64 with one descending sweep — matches, bytes, batches, sweep visits and hop depth per step — so a change to
+either is priced before it is built.
 Restates RFC 1951 decoding in Python (tools/regions_model.py).   resolve_model.py [--blocks 30] [--tile-mb 8]"""
 import argparse
 import collections
@@ -58,6 +62,7 @@ def run_block(tok, span=1024, lanes=64, exact=False, far_first=False):
     ae = sum(1 if k == "l" else v if k == "L" else 0 for k, v in tok)
     tok = tok + [("p", 0)] * (2 * lanes + 2)
     B, tp, steps, rounds, its = 0, 0, 0, 0, 0
+    x = collections.Counter()  # the first round apart, and the two-pass scheme
     while B < ae:
         lanes_ = []
         for i in range(lanes):
@@ -81,6 +86,7 @@ def run_block(tok, span=1024, lanes=64, exact=False, far_first=False):
                 Le = min(Lm, ae - mO)
                 if Le > 0:
                     ms.append((mO, Le, d))
+        two_pass(ms, B, x)
         pend = list(range(len(ms)))
         first = True
         while pend:
@@ -98,12 +104,58 @@ def run_block(tok, span=1024, lanes=64, exact=False, far_first=False):
                     ready.append(j)
             rounds += 1
             its += max(iters(ms[j][1], ms[j][2]) for j in ready)
+            w = "first" if first else "later"
+            x[w + "_matches"] += len(ready)
+            x[w + "_bytes"] += sum(ms[j][1] for j in ready)
+            x[w + "_rounds"] += 1
+            x[w + "_iters"] += max(iters(ms[j][1], ms[j][2]) for j in ready)
             pend = [j for j in pend if j not in ready]
             first = False
         steps += 1
         B = E
         tp = tp + 2 * nt + (1 if lanes_[nt - 1][3] else 0)
-    return steps, rounds, its
+    return steps, rounds, its, x
+
+
+def two_pass(ms, B, x):
+    """One step's matches (mO, Le, d) under the two-pass scheme, added to the counter x."""
+    x["matches"] += len(ms)
+    x["bytes"] += sum(m[1] for m in ms)
+    if not ms:
+        return
+    ind = [m for m in ms if m[0] - m[2] + min(m[1], m[2]) <= B]
+    dep = [m for m in ms if m[0] - m[2] + min(m[1], m[2]) > B]
+    x["ind_matches"] += len(ind)
+    x["ind_wide_matches"] += sum(m[0] - m[2] + min(m[1], m[2]) <= ms[0][0] for m in ms)
+    x["ind_iters"] += max([iters(m[1], m[2]) for m in ind] or [0])
+    nb = sum(m[1] for m in dep)
+    x["dep_matches"] += len(dep)
+    x["dep_bytes"] += nb
+    x["dep_steps"] += bool(dep)
+    x["dep_steps_gt64"] += nb > 64
+    batches = -(-nb // 64)
+    x["dep_batches"] += batches
+    # every batch visits the dependents that still have bytes and all before them: last to first, a batch drops the
+    # dependents it finishes
+    done, k = 0, len(dep)
+    for _ in range(batches):
+        x["sweep_visits"] += k
+        done += 64
+        while k and sum(m[1] for m in dep[k - 1:]) <= done:
+            k -= 1
+    for plain in (False, True):  # hop depth of every dependent byte: with the collapsed source, and without
+        deepest = 0
+        for mO, Le, d in dep:
+            for j in range(0, Le, 1 if Le <= 64 else 7):
+                s, n = mO - d + (j if plain and j < d else j % d), 0
+                if plain and j >= d:  # byte j reads byte j - d of the match itself
+                    n = j // d
+                for qO, qL, qd in reversed(dep):
+                    if qO <= s < qO + qL:
+                        r = s - qO
+                        s, n = qO - qd + r % qd, n + 1 + (r // qd if plain else 0)
+                deepest = max(deepest, n)
+        x["depth_plain" if plain else "depth_collapsed"] += deepest
 
 
 def main():
@@ -124,12 +176,31 @@ def main():
     for name, kw in (("kernel_rule", {}), ("exact_rule", {"exact": True})):
         t = collections.Counter()
         for tk in toks:
-            s, r, i = run_block(tk, span=args.span, **kw)
+            s, r, i, x = run_block(tk, span=args.span, **kw)
             t["steps"] += s
             t["rounds"] += r
             t["iters"] += i
-        res[name] = {"steps": t["steps"], "rounds_per_step": round(t["rounds"] / t["steps"], 3),
-                     "iters_per_step": round(t["iters"] / t["steps"], 3)}
+            t.update(x)
+        n = t["steps"]
+        res[name] = {"steps": n, "rounds_per_step": round(t["rounds"] / n, 3),
+                     "iters_per_step": round(t["iters"] / n, 3),
+                     "first_round": {k: round(t["first_" + k] / n, 3) for k in ("matches", "bytes", "rounds", "iters")},
+                     "later_rounds": {k: round(t["later_" + k] / n, 3) for k in ("matches", "bytes", "rounds", "iters")}}
+        if name == "kernel_rule":
+            res["two_pass"] = {
+                "matches_per_step": round(t["matches"] / n, 3), "bytes_per_step": round(t["bytes"] / n, 1),
+                "independents_per_step": round(t["ind_matches"] / n, 3),
+                "independents_per_step_wide_test": round(t["ind_wide_matches"] / n, 3),
+                "independent_copy_iters_per_step": round(t["ind_iters"] / n, 3),
+                "dependents_per_step": round(t["dep_matches"] / n, 3),
+                "dependent_bytes_per_step": round(t["dep_bytes"] / n, 2),
+                "steps_with_dependents_pct": round(100.0 * t["dep_steps"] / n, 1),
+                "steps_over_64_dependent_bytes_pct": round(100.0 * t["dep_steps_gt64"] / n, 2),
+                "batches_per_step": round(t["dep_batches"] / n, 3),
+                "sweep_visits_per_step": round(t["sweep_visits"] / n, 3),
+                "deepest_hop_chain_per_step_with_dependents": {
+                    "plain": round(t["depth_plain"] / max(t["dep_steps"], 1), 2),
+                    "collapsed": round(t["depth_collapsed"] / max(t["dep_steps"], 1), 2)}}
     print(json.dumps({"blocks": len(toks), "span": args.span, **res}))
 
 

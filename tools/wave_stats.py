@@ -42,13 +42,12 @@ out["b_iters_per_round"] = round(v[7] / max(v[6], 1), 3)
 out["rounds_per_block"] = round(v[6] / out["blocks"], 3)
 out["cycles_per_header"] = {n: round(v[i] / max(v[9], 1)) for i, n in ((0, "rest"), (10, "cl_setup"), (11, "chain"), (12, "stage"), (5, "build_dist"), (1, "build_lit"))}
 out["cycles_per_round"] = {n: round(v[i] / max(v[6], 1)) for i, n in list(enumerate(names[2:6], 2)) + [(13, "warmup")]}
-rsteps = max(v[38], 1)
-rnames = ["positions_zero", "literals", "output_stores", "match_setup", "rounds", "token_wait"]
+rsteps = max(v[39], 1)
+rnames = ["positions_zero", "literals", "output_stores", "match_setup", "independents", "dependents", "token_wait"]
 res = {n: round(v[32 + i] / rsteps) for i, n in enumerate(rnames)}
-res["tail_and_rest"] = round((v[31] - sum(v[32:38])) / rsteps)
+res["tail_and_rest"] = round((v[31] - sum(v[32:39])) / rsteps)
 out["resolve_cycles_per_step"] = res
-out["resolve_steps_per_block"] = round(v[38] / out["blocks"], 2)
-out["resolve_rounds_per_step"] = round(v[39] / rsteps, 3)
+out["resolve_steps_per_block"] = round(v[39] / out["blocks"], 2)
 out["resolve_cycles_per_block"] = round(v[31] / out["blocks"])
 out["resolve_ms"] = f.kernel_ms("inflate_resolve")
 out["resolve_copy_iters_per_step"] = {"wave": round(v[29] / rsteps, 2), "lane_sum": round(v[30] / rsteps, 2),
