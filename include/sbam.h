@@ -196,7 +196,9 @@ int sbam_offset_to_pos(sbam_ctx *ctx, int64_t offset, sbam_pos *pos);
 /* ---- BAM header (check/.../bam/header/Header.scala:26-60; ContigLengths.scala:33-55) ---------- */
 
 /* n_ref and contig lengths (cap entries), end_pos = Header.endPos.  Must follow sbam_inflate on a
- * whole file; a shard takes them from sbam_set_contig_lengths (the broadcast in CanLoadBam.scala:179-180). */
+ * whole file; a shard takes them from sbam_set_contig_lengths (the broadcast in CanLoadBam.scala:179-180).
+ * Any int64 length is valid: the checkers compare refPos > length as the reference does on a Long
+ * (PosChecker.scala:59), also for lengths below 0 or above INT32_MAX. */
 int sbam_header(sbam_ctx *ctx, int32_t *n_ref, int64_t *lengths, int32_t cap, sbam_pos *end_pos);
 int sbam_set_contig_lengths(sbam_ctx *ctx, int32_t n_ref, const int64_t *lengths);
 

@@ -1179,7 +1179,13 @@ int sbam_set_contig_lengths(sbam_ctx *c, int32_t n_ref, const int64_t *lengths) 
   if (!c || n_ref < 0 || (n_ref && !lengths)) return SBAM_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, c->d_lens.ensure((size_t)n_ref));
-  if (n_ref) HIPCHK(c, hipMemcpyAsync(c->d_lens, lengths, n_ref * 8, hipMemcpyHostToDevice, c->stream));
+  // The device table holds the lengths clamped to [-2, INT32_MAX] (h_lens keeps the caller's values).  The kernels
+  // ask only refPos > length for an int32 refPos >= -1 (refPos < -1 is decided before the length is looked at,
+  // PosChecker.scala:43-63), which the clamp leaves unchanged for every int64 length, and the record-0 kernels keep
+  // the table as int32 in LDS.
+  std::vector<int64_t> clamped(lengths, lengths + n_ref);
+  for (int64_t &v : clamped) v = v < -2 ? -2 : v > INT32_MAX ? INT32_MAX : v;
+  if (n_ref) HIPCHK(c, hipMemcpyAsync(c->d_lens, clamped.data(), n_ref * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->h_lens.assign(lengths, lengths + n_ref);
   c->nref = n_ref;

@@ -65,12 +65,13 @@ SB_DEV int32_t g_i32(const uint8_t *u, int64_t x) {
 }
 
 // PosChecker.getRefPosError as bits {negIdx, bigIdx, negPos, bigPos}.  negPos = refPos < -1 in every branch;
-// bigPos only when 0 <= refIdx < n_ref and refPos > len[refIdx] (note '>': refPos == len passes).
+// bigPos only when 0 <= refIdx < n_ref and -1 <= refPos > len[refIdx] (note '>': refPos == len passes).  The table
+// holds the lengths clamped to [-2, INT32_MAX] (sbam_set_contig_lengths): a length below zero fails refPos -1 or 0.
 SB_DEV uint32_t ref_err(int32_t ri, int32_t rp, const int32_t *lensL, const int64_t *lensG, int32_t nref) {
   uint32_t f = (ri < -1) ? 1u : 0u;
   f |= (ri >= nref) ? 2u : 0u;
   f |= (rp < -1) ? 4u : 0u;
-  if ((uint32_t)ri < (uint32_t)nref && rp > 0) {
+  if ((uint32_t)ri < (uint32_t)nref && rp >= -1) {
     const int64_t len = lensL ? (int64_t)lensL[ri] : lensG[ri];
     f |= ((int64_t)rp > len) ? 8u : 0u;
   }

@@ -31,16 +31,30 @@ def filler(n: int) -> bytes:
 
 def record(ref_id: int = -1, pos: int = -1, name: bytes = b"r", mapq: int = 0, bin_: int = 4680, flag: int = 4,
            cigar=(), seq: bytes = b"", qual: bytes = b"", l_seq=None, next_ref_id: int = -1, next_pos: int = -1,
-           tlen: int = 0, aux: bytes = b"", block_size=None, l_read_name=None, n_cigar_op=None) -> bytes:
-    """One record.  `name` is written with its NUL; `cigar` holds raw uint32 ops (len << 4 | op); `seq` the packed
-    bases; l_seq, l_read_name, n_cigar_op and block_size default to what the bytes say and can each be overridden."""
-    nm = name + b"\x00"
+           tlen: int = 0, aux: bytes = b"", block_size=None, l_read_name=None, n_cigar_op=None,
+           raw_name=None) -> bytes:
+    """One record.  `name` is written with its NUL (`raw_name`, when given, replaces both: the name field's bytes as
+    they stand, with or without a NUL); `cigar` holds raw uint32 ops (len << 4 | op); `seq` the packed bases; l_seq,
+    l_read_name, n_cigar_op and block_size default to what the bytes say and can each be overridden."""
+    nm = name + b"\x00" if raw_name is None else bytes(raw_name)
     lrn = len(nm) if l_read_name is None else l_read_name
     nc = len(cigar) if n_cigar_op is None else n_cigar_op
     ls = len(qual) if l_seq is None else l_seq
     body = struct.pack("<iiBBHHHiiii", ref_id, pos, lrn, mapq, bin_, nc, flag, ls, next_ref_id, next_pos, tlen)
     body += nm + b"".join(struct.pack("<I", op) for op in cigar) + seq + qual + aux
     return struct.pack("<i", len(body) if block_size is None else block_size) + body
+
+
+def _i32(v: int) -> int:
+    return (v + 2**31) % 2**32 - 2**31
+
+
+def implied_size(l_read_name: int, n_cigar_op: int, l_seq: int) -> int:
+    """The least block_size full/Checker.scala:68-71 accepts: 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq
+    in Java Int arithmetic (every sum wraps at 32 bits, '/' truncates toward zero)."""
+    t = _i32(l_seq + 1)
+    half = -(-t // 2) if t < 0 else t // 2
+    return _i32(32 + l_read_name + 4 * n_cigar_op + _i32(half + l_seq))
 
 
 def sized(n: int, **kw) -> bytes:
