@@ -499,6 +499,40 @@ int sbam_write_bai(sbam_ctx *ctx, uint8_t *out, int64_t cap, int64_t *n_bytes);
  * no reference counterpart, Index.scala:53-90 only reads): for tests that must reach that path. */
 int sbam_index_long_cigar_ops(void);
 
+/* ---- Coordinate sort of the loaded records (no reference counterpart: the reference never reorders records; the
+ * behaviour mirrored is htsjdk's SAMFileWriterFactory with SortOrder.coordinate behind HTSJDKRewrite.scala:52-76, and
+ * `samtools sort`) ------------------------------------------------------------------------------------------------
+ * The key of loaded record r is the 64-bit unsigned word
+ *   (uint64_t)(uint32_t)ref_id[r] << 32 | (uint32_t)(pos[r] ^ 0x80000000):
+ * references ascend as unsigned, so ref_id == -1 (no coordinate) sorts last; within a reference pos ascends as signed,
+ * so -1 sorts first.  Records with equal keys keep their loaded (file) order: the sort is stable, and the order a
+ * function of the two columns alone.  This is the order sbam_build_index's n_unsorted tests and the one htsjdk and
+ * samtools accept as SO:coordinate; it is not `samtools sort`'s tie order, which adds the strand bit.  Queryname and
+ * tag orders, and merging sorted runs of a file larger than device memory, are not built. */
+typedef struct {
+  int64_t n_records;       /* records sorted (the loaded ones) */
+  int64_t n_out_of_order;  /* before the sort: records whose key is below their predecessor's; 0: order = identity */
+  int32_t passes;          /* radix passes that ran, 0..8 */
+  int32_t reserved;
+} sbam_sort_totals;
+
+/* Sort the records of the last sbam_load_records by coordinate on the GPU (no reference counterpart; htsjdk
+ * SortOrder.coordinate): an LSD radix sort of (key, index) pairs by bytes; a byte that is the same in every key costs no
+ * pass, and an input already in order none at all.  SBAM_ERR_STATE without loaded records; no records is SBAM_OK;
+ * 2^32 records or more: SBAM_ERR_ARG.  The order lives on the device, owned by ctx (grow-only buffers sized by one rule:
+ * 32 bytes per record and 8 per 2048-key tile and digit; sbam_reserve serves streamed windows and does not size them),
+ * until the next sbam_sort_records, sbam_load_records, load, reset or close; fields, tags, an index or a write do not
+ * invalidate it.  sbam_last_kernel_ms: "sort_keys" (keys and histograms), "sort" (the whole call). */
+int sbam_sort_records(sbam_ctx *ctx, sbam_sort_totals *totals);
+/* Entries [i0, i0 + n) of the last sort's order into a host buffer: order[k] = loaded index of the k-th record in
+ * coordinate order (no reference counterpart; what htsjdk's coordinate-sorting writer emits k-th). */
+int sbam_get_sort_order(sbam_ctx *ctx, int64_t i0, int64_t n, int64_t *order);
+/* The same column on the device, *n entries (no reference counterpart; for in-process GPU consumers; no copy). */
+int sbam_sort_order_device(sbam_ctx *ctx, const int64_t **order, int64_t *n);
+/* Keys per workgroup tile of the sort's passes, a build constant (no reference counterpart): for tests that must reach
+ * the tile's edges and more tiles than one workgroup of the scan covers. */
+int sbam_sort_tile_keys(void);
+
 /* ---- BAM writer: records of the last sbam_load_records -> BGZF bytes on the device ------------------------------
  * htsjdk-rewrite (cli/src/main/scala/org/hammerlab/bam/rewrite/HTSJDKRewrite.scala:21-91): the BAM header, then the
  * selected records back to back, cut every block_bytes uncompressed bytes (htsjdk's 65498), each piece deflated and
@@ -539,6 +573,24 @@ typedef struct {
  * block_bytes + 13 rounded up to 16 each; with SBAM_WRITE_DYNAMIC the token records, one per resident wavefront, at
  * most 1024, of two bytes per block byte + 2 rounded up to 16), until the next sbam_write_bam, load, reset or close. */
 int sbam_write_bam(sbam_ctx *ctx, const sbam_write_args *args, sbam_write_totals *totals);
+typedef struct {
+  const int64_t *order_device; /* device, n_loaded entries: entry k of the output is loaded record order_device[k];
+                                  NULL: the order of the last sbam_sort_records (SBAM_ERR_STATE when there is none) */
+  const uint8_t *header;       /* host, optional: a complete BAM header (magic .. last reference) written instead of the
+                                  stream's; only with with_header = 1, and then the context need not start at offset 0 */
+  int64_t header_bytes;
+} sbam_write_order;
+/* sbam_write_bam with one indirection in its select step (no reference counterpart; htsjdk's SAMFileWriterFactory with
+ * SortOrder.coordinate behind HTSJDKRewrite.scala:52-76, and `samtools sort`, when the order is a sort's).  args->range_*
+ * and keep_device still index the loaded records: a record is written when its own index is selected, and the order
+ * only decides the sequence.  ord == NULL: sbam_write_bam.  Checked before anything is written: every order_device entry
+ * lies in [0, n_loaded), on the device, else SBAM_ERR_ARG (the previous written bytes are gone, as after any failed
+ * write); a repeated entry is no error: that record is written twice.  The override header is checked on the host:
+ * the magic, and l_text, n_ref and the names' lengths must add up to exactly header_bytes, else SBAM_ERR_ARG; so is a
+ * header with with_header = 0, header_bytes without a header, or a header longer than the context's uncompressed
+ * stream + 16368 bytes.  Totals, buffers and the getters below as for sbam_write_bam. */
+int sbam_write_bam_ordered(sbam_ctx *ctx, const sbam_write_args *args, const sbam_write_order *ord,
+                           sbam_write_totals *totals);
 /* The file bytes of the last sbam_write_bam (what HTSJDKRewrite.scala:52-76 leaves at its output path); cap smaller
  * than comp_bytes: SBAM_ERR_ARG. */
 int sbam_get_written(sbam_ctx *ctx, uint8_t *out, int64_t cap);
@@ -560,6 +612,11 @@ int sbam_get_written_records(sbam_ctx *ctx, int64_t *block_pos, int32_t *block_o
  * rule (the file ubytes + 31 per block + 28, slots and token records per batch). */
 int sbam_test_deflate(int device, const uint8_t *in, int64_t n, int32_t block_bytes, int32_t level, int32_t with_eof,
                       uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_stored_blocks);
+
+/* ---- for tests: the coordinate sort over arbitrary keys (no reference counterpart; no context: the call allocates
+ * its device buffers, runs on a stream of its own, copies back and frees): order receives the stable order of the n
+ * keys (order[k] = index of the k-th smallest, ties by index), *passes the radix passes that ran. */
+int sbam_test_sort_keys(int device, const uint64_t *keys, int64_t n, int64_t *order, int32_t *passes);
 
 /* ---- for tests: the library's prefix-sum primitives (no reference counterpart; no context: each call allocates its
  * device buffers, runs on a stream of its own, copies back and frees) ------------------------------------------- */
@@ -589,7 +646,8 @@ int sbam_test_chain_proof(int device, const uint8_t *u, int64_t L, const uint64_
  * through the linear index's fill), "crc" (the block CRC32 check), "record_tags" (sbam_load_record_tags: its walk and
  * scans, "record_tag_walk", plus the gather of its byte columns, "record_tag_bytes"), "write_select", "write_gather",
  * "write_deflate", "write_frame" (sbam_write_bam's stages; deflate and frame: of its last batch of blocks; the deflate
- * stage is one launch at every level, SBAM_WRITE_DYNAMIC's tokens, codes and emit included). Returns -1 if none. */
+ * stage is one launch at every level, SBAM_WRITE_DYNAMIC's tokens, codes and emit included), "sort_keys" and "sort"
+ * (sbam_sort_records: its keys and histograms; the whole call). Returns -1 if none. */
 double sbam_last_kernel_ms(sbam_ctx *ctx, const char *kernel);
 
 #ifdef __cplusplus

@@ -211,10 +211,12 @@ struct BlockMirror {
 //   record_count, proof_fail   sbam_record_offsets; split_counts (an int32 flag)
 //   arena_used                 TokPool::arena_used
 //   crc_bad, crc_first_bad     run_crc (written and read back as one pair)
+//   order_bad                  sbam_write_bam_ordered: an entry of the caller's order outside the loaded records
 struct Scratch {
   int64_t scan_total, scan_overflow, table_first, chain_stop, inflate_error, record_count, proof_fail, arena_used;
   int64_t crc_bad, crc_first_bad;
   int64_t follow_bad, follow_stop, follow_total;
+  int64_t order_bad;
 };
 
 }  // namespace
@@ -316,6 +318,12 @@ struct sbam_ctx {
   sbam_index_totals idx_tot{};
   IndexStats istat{};  // d_istat, carved (index_words)
   std::vector<int64_t> idx_intv;  // n_ref + 1 window offsets
+  // coordinate order of the last sbam_sort_records: the order column with the sort's ping-pong buffers, counts and
+  // histogram words in one arena (sort_bufs)
+  DevBuf<uint8_t> d_sort;
+  SortBufs sbuf{};
+  bool sorted = false;
+  sbam_sort_totals sort_tot{};
   // BAM of the last sbam_write_bam: the selection's columns (write_sel), the ranges, the gather's tiles, the blocks
   // stage, and the written records' Pos columns
   DevBuf<uint8_t> d_wsel;
@@ -400,11 +408,11 @@ void set_bitmap(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, bool list_form) 
 void drop_bitmap(sbam_ctx *c) { c->bm_valid = c->bm_list = c->rp_fetch = false; }
 
 // The stages a context can hold, in the order they are made: candidates -> table -> stream -> {crc, bitmap, records},
-// records -> {fields, tags, index, written}.  (The table comes from the followed hops, or from the candidates; a
+// records -> {fields, tags, index, written, sorted}.  (The table comes from the followed hops, or from the candidates; a
 // context can hold one without the candidates, never a later stage without the table.)  A producer drops its own
 // stage, and with it everything made from it, before it touches a buffer (drop_from), and sets its stage's validity
 // field as its last step; nothing else clears one.
-enum Stage { kCandidates, kTable, kStream, kCrc, kBitmap, kRecords, kFields, kTags, kIndex, kWritten };
+enum Stage { kCandidates, kTable, kStream, kCrc, kBitmap, kRecords, kFields, kTags, kIndex, kWritten, kSorted };
 bool any_stage_ran(const sbam_ctx *c) { return c->ncand >= 0 || c->blk.n >= 0 || c->L >= 0 || c->n_loaded >= 0; }
 // Returns the table mirror's invalidate() (a wait for a copy in flight), hipSuccess for every other stage.
 hipError_t drop_from(sbam_ctx *c, Stage from) {
@@ -420,6 +428,7 @@ hipError_t drop_from(sbam_ctx *c, Stage from) {
   if (records || from == kTags) c->t_n = -1;
   if (records || from == kIndex) c->idx_built = false;
   if (records || from == kWritten) c->w.ubytes = -1;
+  if (records || from == kSorted) c->sorted = false;
   return e;
 }
 
@@ -496,6 +505,40 @@ hipError_t ensure_index(sbam_ctx *c, size_t N, bool *grew = nullptr) {
   HIPTRY(c->d_iend.ensure(N, grew));
   HIPTRY(c->d_ibin.ensure(N, grew));
   return c->d_iheads.ensure((size_t)index_blocks((int64_t)N) + 1, grew);
+}
+
+// the coordinate sort of N records (sort_bufs), carved into *b; sbam_reserve serves streamed windows and does not size
+// it (as for the index)
+hipError_t ensure_sort(DevBuf<uint8_t> &buf, size_t N, SortBufs *b, bool *grew = nullptr) {
+  const int64_t tiles = sort_tiles((int64_t)N);
+  return carve(buf, grew, [&](Carve &k) {
+    *b = sort_bufs<SortBufs>(k, N, (size_t)tiles, (size_t)exclusive_scan_blocks(tiles), kSortHistWords);
+  });
+}
+
+// The sort of n keys, b.keys[0] built from the columns (ref_id non-null) or already there: the histograms decide which
+// passes run (none when no key is below its predecessor: the identity), and b.order receives the stable order.
+// tc: the context whose timer records the keys stage (nullptr: none).  Synchronises s once, for the histograms.
+hipError_t sort_run(const SortBufs &b, const int32_t *ref_id, const int32_t *pos, int64_t n, hipStream_t s, sbam_ctx *tc,
+                    int64_t *out_of_order, int32_t *passes) {
+  std::vector<unsigned long long> h(kSortHistWords, 0);
+  {
+    Timer t(tc, "sort_keys");
+    HIPTRY(launch_sort_keys(ref_id, pos, n, b, s));
+  }
+  HIPTRY(hipMemcpyAsync(h.data(), b.hist, h.size() * 8, hipMemcpyDeviceToHost, s));
+  HIPTRY(hipStreamSynchronize(s));
+  *out_of_order = (int64_t)h[kSortHistWords - 1];
+  int run[8], np = 0;
+  for (int p = 0; p < 8 && *out_of_order; p++) {
+    bool constant = false;  // one bin holds every key: the pass would move nothing
+    for (int d = 0; d < 256; d++) constant |= h[p * 256 + d] == (unsigned long long)n;
+    if (!constant) run[np++] = p;
+  }
+  *passes = np;
+  if (!np) return launch_sort_identity(b.order, n, s);
+  for (int j = 0; j < np; j++) HIPTRY(launch_sort_pass(b, n, run[j], j & 1, j == 0, j == np - 1, s));
+  return hipSuccess;
 }
 
 // The BAM writer.  Its scratch is bounded by the batch, its results by what they hold:
@@ -2151,8 +2194,73 @@ int sbam_write_bai(sbam_ctx *c, uint8_t *out, int64_t cap, int64_t *n_bytes) {
   return SBAM_OK;
 }
 
+// ---- coordinate sort (no reference counterpart; htsjdk SortOrder.coordinate, sbam_sort_core.h) --------------------
+int sbam_sort_tile_keys(void) { return kSortTile; }
+
+int sbam_sort_records(sbam_ctx *c, sbam_sort_totals *totals) {
+  if (!c) return SBAM_ERR_ARG;
+  if (c->n_loaded < 0) return set_err(c, SBAM_ERR_STATE, "sbam_load_records has not run");
+  const int64_t N = c->n_loaded;
+  if (N >= (1ll << 32)) return set_err(c, SBAM_ERR_ARG, "%lld records: the sort carries 32-bit indices", (long long)N);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, drop_from(c, kSorted));
+  HIPCHK(c, ensure_sort(c->d_sort, (size_t)N, &c->sbuf));
+  int64_t below = 0;
+  int32_t passes = 0;
+  {
+    Timer t(c, "sort");
+    HIPCHK(c, sort_run(c->sbuf, c->rcols.ref_id, c->rcols.pos, N, c->stream, c, &below, &passes));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->sort_tot = sbam_sort_totals{N, below, passes, 0};
+  c->sorted = true;
+  if (totals) *totals = c->sort_tot;
+  return SBAM_OK;
+}
+
+int sbam_get_sort_order(sbam_ctx *c, int64_t i0, int64_t n, int64_t *order) {
+  if (!c || i0 < 0 || n < 0 || (n && !order)) return SBAM_ERR_ARG;
+  if (!c->sorted) return set_err(c, SBAM_ERR_STATE, "sbam_sort_records has not run");
+  if (i0 + n > c->sort_tot.n_records)
+    return set_err(c, SBAM_ERR_ARG, "entries [%lld, %lld) past %lld sorted", (long long)i0, (long long)(i0 + n),
+                   (long long)c->sort_tot.n_records);
+  if (!n) return SBAM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpy(order, c->sbuf.order + i0, (size_t)n * 8, hipMemcpyDeviceToHost));
+  return SBAM_OK;
+}
+
+int sbam_sort_order_device(sbam_ctx *c, const int64_t **order, int64_t *n) {
+  if (!c || !order || !n) return SBAM_ERR_ARG;
+  if (!c->sorted) return set_err(c, SBAM_ERR_STATE, "sbam_sort_records has not run");
+  *order = c->sbuf.order;
+  *n = c->sort_tot.n_records;
+  return SBAM_OK;
+}
+
 // ---- BAM writer (htsjdk-rewrite, cli/.../bam/rewrite/HTSJDKRewrite.scala:21-91) ---------------------------------
-int sbam_write_bam(sbam_ctx *c, const sbam_write_args *a, sbam_write_totals *totals) {
+// A complete BAM header (SAM spec §4.2: magic, l_text, text, n_ref, then l_name, name, l_ref per reference) of exactly
+// n bytes?
+static bool bam_header_adds_up(const uint8_t *h, int64_t n) {
+  auto i32 = [&](int64_t at) { int32_t v; std::memcpy(&v, h + at, 4); return v; };
+  if (!h || n < 12 || std::memcmp(h, "BAM\1", 4) != 0) return false;
+  const int64_t l_text = i32(4);
+  if (l_text < 0 || 8 + l_text + 4 > n) return false;
+  int64_t at = 8 + l_text;
+  const int64_t n_ref = i32(at);
+  at += 4;
+  if (n_ref < 0) return false;
+  for (int64_t r = 0; r < n_ref; r++) {
+    if (at + 4 > n) return false;
+    const int64_t l_name = i32(at);
+    if (l_name < 0 || at + 4 + l_name + 4 > n) return false;
+    at += 4 + l_name + 4;
+  }
+  return at == n;
+}
+
+// sbam_write_bam (ord null) and sbam_write_bam_ordered: one writer, the order one indirection in its select step
+static int write_bam(sbam_ctx *c, const sbam_write_args *a, const sbam_write_order *ord, sbam_write_totals *totals) {
   if (!c || !a) return SBAM_ERR_ARG;
   if (c->n_loaded < 0 || c->L < 0) return set_err(c, SBAM_ERR_STATE, "sbam_load_records has not run");
   const int64_t N = c->n_loaded;
@@ -2169,11 +2277,35 @@ int sbam_write_bam(sbam_ctx *c, const sbam_write_args *a, sbam_write_totals *tot
       return set_err(c, SBAM_ERR_ARG, "range %lld [%lld, %lld): out of order or outside the %lld loaded records",
                      (long long)r, (long long)lo, (long long)hi, (long long)N);
   }
-  if (a->with_header && (c->base != 0 || c->header_x < 0))
+  const uint8_t *header = ord ? ord->header : nullptr;
+  if (ord && !header && ord->header_bytes != 0) return set_err(c, SBAM_ERR_ARG, "header_bytes without a header");
+  if (header) {
+    if (!a->with_header) return set_err(c, SBAM_ERR_ARG, "a header override needs with_header = 1");
+    if (!bam_header_adds_up(header, ord->header_bytes))
+      return set_err(c, SBAM_ERR_ARG, "header override: not a BAM header of exactly %lld bytes (magic, l_text, n_ref, names)",
+                     (long long)ord->header_bytes);
+    // (the gather copies entry 0 from the stream's first bytes before the override replaces them: they must be readable)
+    if (ord->header_bytes + 16 > c->L + kStreamPad)
+      return set_err(c, SBAM_ERR_ARG, "header override of %lld bytes: at most %lld (the stream's length + %d)",
+                     (long long)ord->header_bytes, (long long)(c->L + kStreamPad - 16), kStreamPad - 16);
+  } else if (a->with_header && (c->base != 0 || c->header_x < 0)) {
     return set_err(c, SBAM_ERR_STATE, "with_header needs a context that starts at file offset 0 and has read its header");
+  }
+  const int64_t *order = ord ? ord->order_device : nullptr;
+  if (ord && !order) {
+    if (!c->sorted) return set_err(c, SBAM_ERR_STATE, "sbam_sort_records has not run (and no order_device given)");
+    order = c->sbuf.order;
+  }
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, drop_from(c, kWritten));
-  const int64_t header_bytes = a->with_header ? c->header_x : 0;
+  if (ord && ord->order_device) {  // the caller's entries, checked on the device before anything is written
+    int32_t bad = 0;
+    HIPCHK(c, launch_order_check(order, N, N, reinterpret_cast<int32_t *>(SMALL(c, order_bad)), c->stream));
+    HIPCHK(c, hipMemcpyAsync(&bad, SMALL(c, order_bad), 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (bad) return set_err(c, SBAM_ERR_ARG, "order_device: an entry outside the %lld loaded records", (long long)N);
+  }
+  const int64_t header_bytes = header ? ord->header_bytes : a->with_header ? c->header_x : 0;
   WriteSel sl;
   HIPCHK(c, carve(c->d_wsel, nullptr, [&](Carve &k) { sl = write_sel(k, N, exclusive_scan_blocks(N + 1)); }));
   HIPCHK(c, c->d_wrange.ensure((size_t)(2 * a->n_ranges)));
@@ -2185,7 +2317,7 @@ int sbam_write_bam(sbam_ctx *c, const sbam_write_args *a, sbam_write_totals *tot
   {
     Timer t(c, "write_select");
     const WriteSelectArgs sa{c->d_roff, c->rcols.block_size, N, c->L, c->d_wrange, c->d_wrange + a->n_ranges,
-                             a->n_ranges, a->keep_device, header_bytes, sl.len, sl.cnt, sl.src};
+                             a->n_ranges, a->keep_device, header_bytes, sl.len, sl.cnt, sl.src, order};
     HIPCHK(c, launch_write_select(sa, c->stream));
     HIPCHK(c, launch_exclusive_scan(sl.len, (int64_t)sl.stride, N + 1, 2, sl.bsum, sl.tot, c->stream));
   }
@@ -2201,6 +2333,7 @@ int sbam_write_bam(sbam_ctx *c, const sbam_write_args *a, sbam_write_totals *tot
     const FieldGatherArgs ga{c->d_u, nullptr, nullptr, nullptr, nullptr, sl.len,       N + 1,
                              0,      ubytes,  c->w.u,  c->d_wtiles, sl.src};
     HIPCHK(c, launch_field_gather(5, ga, c->stream));
+    if (header) HIPCHK(c, hipMemcpyAsync(c->w.u, header, (size_t)header_bytes, hipMemcpyHostToDevice, c->stream));
   }
   HIPCHK(c, writer_run(c->w, c->stream, c, ubytes, bb, a->level, a->with_eof != 0));
   HIPCHK(c, c->d_wrpos.ensure((size_t)n_records));
@@ -2211,6 +2344,15 @@ int sbam_write_bam(sbam_ctx *c, const sbam_write_args *a, sbam_write_totals *tot
   c->w.ubytes = ubytes;
   if (totals) *totals = c->w_tot;
   return SBAM_OK;
+}
+
+int sbam_write_bam(sbam_ctx *c, const sbam_write_args *a, sbam_write_totals *totals) {
+  return write_bam(c, a, nullptr, totals);
+}
+
+int sbam_write_bam_ordered(sbam_ctx *c, const sbam_write_args *a, const sbam_write_order *ord,
+                           sbam_write_totals *totals) {
+  return write_bam(c, a, ord, totals);
 }
 
 int sbam_get_written(sbam_ctx *c, uint8_t *out, int64_t cap) {
@@ -2305,6 +2447,25 @@ int sbam_test_scan_sums_int(int device, const int32_t *in, int64_t n, int64_t *o
   if (e == hipSuccess) e = launch_scan_sums(d_in, d_out, n, 1, d_out + n, t.stream);
   if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (N + 1) * 8, hipMemcpyDeviceToHost, t.stream);
   if (e == hipSuccess) e = hipStreamSynchronize(t.stream);
+  return e == hipSuccess ? SBAM_OK : SBAM_ERR_HIP;
+}
+
+// The sort (sort_run: keys' histograms, the passes they leave, the order) over the caller's keys, on buffers and a
+// stream of the call's own.
+int sbam_test_sort_keys(int device, const uint64_t *keys, int64_t n, int64_t *order, int32_t *passes) {
+  if (n < 0 || n >= (1ll << 32) || !passes || (n && (!keys || !order))) return SBAM_ERR_ARG;
+  if (hipSetDevice(device) != hipSuccess) return SBAM_ERR_HIP;
+  DevBuf<uint8_t> buf;  // (freed on every path, with this device current)
+  SortBufs b{};
+  hipStream_t s = nullptr;
+  if (hipStreamCreate(&s) != hipSuccess) return SBAM_ERR_HIP;
+  int64_t below = 0;
+  hipError_t e = ensure_sort(buf, (size_t)n, &b);
+  if (e == hipSuccess && n) e = hipMemcpyAsync(b.keys[0], keys, (size_t)n * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = sort_run(b, nullptr, nullptr, n, s, nullptr, &below, passes);
+  if (e == hipSuccess && n) e = hipMemcpyAsync(order, b.order, (size_t)n * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipStreamDestroy(s);
   return e == hipSuccess ? SBAM_OK : SBAM_ERR_HIP;
 }
 

@@ -315,6 +315,31 @@ int64_t exclusive_scan_blocks(int64_t n);
 hipError_t launch_exclusive_scan(int64_t *off, int64_t stride, int64_t n, int32_t cols, int64_t *bsum, int64_t *totals,
                                  hipStream_t s);
 
+// Coordinate sort (sbam_sort.hip): a stable LSD radix sort of (key, index) pairs, 8-bit digits.  The tile is a build
+// constant (sbam_sort_tile_keys): a multiple of 256, at most 8192.
+#ifndef SBAM_SORT_TILE
+#define SBAM_SORT_TILE 2048
+#endif
+constexpr int kSortTile = SBAM_SORT_TILE;
+constexpr int kSortHistWords = 8 * 256 + 1;  // the eight digit histograms, then the out-of-order count
+struct SortBufs {  // (sbam_layout.h: sort_bufs)
+  uint64_t *keys[2];         // n each: ping and pong
+  uint32_t *idx[2];          // n each (the kernels carry 32-bit indices: n < 2^32)
+  int64_t *order;            // n: the result
+  int64_t *cnt;              // 256 columns of sort_tiles(n) + 1: a pass's per-tile digit counts, scanned in place
+  int64_t *bsum;             // 256 * exclusive_scan_blocks(sort_tiles(n)): the scan's scratch
+  int64_t *totals, *dbase;   // 256: the columns' totals; 257: their exclusive sums (the buckets' bases) and the total
+  unsigned long long *hist;  // kSortHistWords
+};
+int64_t sort_tiles(int64_t n);
+// keys[0] (ref_id non-null: built from the columns; null: already there), and hist filled
+hipError_t launch_sort_keys(const int32_t *ref_id, const int32_t *pos, int64_t n, const SortBufs &b, hipStream_t s);
+// one pass by byte `pass` from keys[src], idx[src] to the other pair (first: idx[src] is the identity and not read;
+// last: the indices go to order as int64, the keys nowhere)
+hipError_t launch_sort_pass(const SortBufs &b, int64_t n, int pass, int src, bool first, bool last, hipStream_t s);
+hipError_t launch_sort_identity(int64_t *order, int64_t n, hipStream_t s);
+// *flag (an 8-byte word, read as int32) = 1 when an entry of order[0, n) lies outside [0, limit), else 0
+hipError_t launch_order_check(const int64_t *order, int64_t n, int64_t limit, int32_t *flag, hipStream_t s);
 
 // BAM writer (sbam_write.hip): select -> (launch_exclusive_scan, launch_field_gather field 5) -> deflate -> frame.
 struct WriteSelectArgs {
@@ -327,6 +352,8 @@ struct WriteSelectArgs {
   int64_t header_bytes;          // stream bytes [0, header_bytes) go first (entry 0 of the columns)
   int64_t *len, *cnt;            // n + 1 values each (room for n + 2: the scan adds the total): bytes and 0 / 1
   int64_t *src;                  // n + 1: each entry's source position in the stream
+  const int64_t *order = nullptr;  // device, n entries: entry 1 + k is record order[k] (null: record k); ranges and
+                                   // keep still index the loaded records
 };
 hipError_t launch_write_select(const WriteSelectArgs &a, hipStream_t s);
 // Pos of the written records from the scanned columns (off, ord: n + 2 entries each) and the written block starts

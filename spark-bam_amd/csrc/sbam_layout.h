@@ -88,6 +88,22 @@ R index_words(Carve &k, size_t nref) {
   return R{k.w64(4), k.w64(nref, 8), k.w64(nref, 8), k.w64(nref, 8), k.w64(nref, 8), k.w64(nref, 8)};
 }
 
+// The coordinate sort of n keys as R = SortBufs: the order, the ping-pong keys and 32-bit indices, a pass's digit
+// counts (256 columns of tiles + 1), the scan's scratch (nblk = exclusive_scan_blocks(tiles) per column), the 256
+// totals, their 257 sums, and the histogram words (hist_words: eight histograms and the out-of-order count)
+template <class R>
+R sort_bufs(Carve &k, size_t n, size_t tiles, size_t nblk, size_t hist_words) {
+  R r{};
+  r.order = k.i64(n);
+  r.keys[0] = k.take<uint64_t>(n), r.keys[1] = k.take<uint64_t>(n);
+  r.idx[0] = k.take<uint32_t>(n), r.idx[1] = k.take<uint32_t>(n);
+  r.cnt = k.i64(256 * (tiles + 1));
+  r.bsum = k.i64(256 * nblk);
+  r.totals = k.i64(256), r.dbase = k.i64(257);
+  r.hist = k.w64(hist_words);
+  return r;
+}
+
 // The writer's selection over n loaded records, one run: the length and the 0-1 column (n + 1 entries and the scan's
 // total each, stride apart), each entry's source, the scan's scratch (nblk = exclusive_scan_blocks(n + 1) per column)
 // and the two totals

@@ -4,7 +4,8 @@
 // through htsjdk's SAMFileWriter, whose BlockCompressedOutputStream cuts the uncompressed stream (header, then the
 // records back to back) every 65 498 bytes, deflates each piece and frames it as a BGZF block.  Here:
 //
-//   select   one thread per loaded record: selected (inside a range, and kept) -> its length 4 + block_size and a 1 into
+//   select   one thread per entry (loaded record k, or record order[k] of an ordered write): selected (inside a range,
+//            and kept, both by the record's loaded index) -> its length 4 + block_size and a 1 into
 //            two int64 columns, which launch_exclusive_scan turns into each record's offset in the output stream and
 //            its ordinal among the written records.  Entry 0 of the columns is the BAM header, a pseudo-record at
 //            stream offset 0.  The bytes are then copied by sbam_fields.hip's gather (field 5: work divided over
@@ -68,11 +69,14 @@ __global__ void __launch_bounds__(kSelectThreads) k_write_select(WriteSelectArgs
   if (i > a.n) return;
   int64_t len = a.header_bytes, cnt = 0, src = 0;
   if (i > 0) {
-    const int64_t r = i - 1;
+    int64_t r = i - 1;
+    if (a.order) r = a.order[r];
+    const bool known = (uint64_t)r < (uint64_t)a.n;  // (the host has checked a caller's order before this launch)
+    r = known ? r : 0;
     const int32_t bs = a.block_size[r];
     src = a.roff[r];
     len = 4 + (int64_t)(bs < 0 ? 0 : bs);
-    bool sel = in_ranges(a.range_lo, a.range_hi, a.n_ranges, r) && (!a.keep || a.keep[r] != 0);
+    bool sel = known && in_ranges(a.range_lo, a.range_hi, a.n_ranges, r) && (!a.keep || a.keep[r] != 0);
     sel = sel && src >= 0 && src + len <= a.L;  // (every loaded record lies inside the stream)
     len = sel ? len : 0;
     cnt = sel ? 1 : 0;
@@ -82,7 +86,7 @@ __global__ void __launch_bounds__(kSelectThreads) k_write_select(WriteSelectArgs
   a.src[i] = src;
 }
 
-// Pos of every written record: entry 1 + r of the scanned columns is record r's stream offset and ordinal
+// Pos of every written record: entry 1 + k of the scanned columns is the k-th entry's stream offset and ordinal
 __global__ void __launch_bounds__(kSelectThreads) k_written_records(const int64_t *__restrict__ off,
                                                                     const int64_t *__restrict__ ord, int64_t n,
                                                                     int32_t block_bytes,

@@ -183,6 +183,15 @@ class _WriteTotals(ctypes.Structure):
                                               "comp_bytes")]
 
 
+class _SortTotals(ctypes.Structure):
+    _fields_ = [("n_records", ctypes.c_int64), ("n_out_of_order", ctypes.c_int64), ("passes", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class _WriteOrder(ctypes.Structure):
+    _fields_ = [("order_device", ctypes.c_void_p), ("header", ctypes.c_void_p), ("header_bytes", ctypes.c_int64)]
+
+
 WRITE_BLOCK_BYTES = 65498  # htsjdk's uncompressed bytes per BGZF block
 
 
@@ -290,6 +299,12 @@ _SIGNATURES = {  # (restype, argtypes) of every symbol include/sbam.h declares
     "sbam_write_bai": (ctypes.c_int, [_vp, _vp, _i64, _P(_i64)]),
     "sbam_index_long_cigar_ops": (ctypes.c_int, []),
     "sbam_write_bam": (ctypes.c_int, [_vp, _P(_WriteArgs), _P(_WriteTotals)]),
+    "sbam_write_bam_ordered": (ctypes.c_int, [_vp, _P(_WriteArgs), _P(_WriteOrder), _P(_WriteTotals)]),
+    "sbam_sort_records": (ctypes.c_int, [_vp, _P(_SortTotals)]),
+    "sbam_get_sort_order": (ctypes.c_int, [_vp, _i64, _i64, _vp]),
+    "sbam_sort_order_device": (ctypes.c_int, [_vp, _P(_vp), _P(_i64)]),
+    "sbam_sort_tile_keys": (ctypes.c_int, []),
+    "sbam_test_sort_keys": (ctypes.c_int, [ctypes.c_int, _vp, _i64, _vp, _P(_i32)]),
     "sbam_get_written": (ctypes.c_int, [_vp, _vp, _i64]),
     "sbam_written_device": (ctypes.c_int, [_vp, _P(_vp), _P(_i64)]),
     "sbam_get_written_blocks": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
@@ -708,6 +723,13 @@ class BamFile:
         self.header_end = _pos(end)
         return self.n_ref, self.contig_lengths, self.header_end
 
+    def header_bytes(self) -> bytes:
+        """The file's BAM header as it lies in the stream: magic through the last reference (what write_bam puts first,
+        and what sam.header_with_sort_order rewrites)."""
+        if self.header_end is None:
+            self.header()
+        return self.read_uncompressed(0, self.offset_of(self.header_end))
+
     def set_contig_lengths(self, lens: Sequence[int]):
         a = np.asarray(lens, np.int64)
         self._check(self.L.sbam_set_contig_lengths(self.ctx, a.size, _ptr(a)))
@@ -988,6 +1010,24 @@ class BamFile:
         self._check(self.L.sbam_write_bai(self.ctx, _ptr(out), out.size, ctypes.byref(n)))
         return out.tobytes()
 
+    # ---- coordinate sort
+    def sort_records(self) -> dict:
+        """sbam_sort_records: the stable coordinate order of the loaded records ((uint32) ref_id, then pos; ties in
+        loaded order), on the GPU.  Returns the totals: n_records, n_out_of_order (before the sort), passes."""
+        t = _SortTotals()
+        self._check(self.L.sbam_sort_records(self.ctx, ctypes.byref(t)))
+        return {k: int(getattr(t, k)) for k, _ in _SortTotals._fields_ if k != "reserved"}
+
+    def sort_order(self, i0: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Entries [i0, i0 + n) of the last sort_records' order (int64): order[k] = loaded index of the k-th record."""
+        if n is None:
+            p, total = ctypes.c_void_p(), ctypes.c_int64(0)
+            self._check(self.L.sbam_sort_order_device(self.ctx, ctypes.byref(p), ctypes.byref(total)))
+            n = total.value - i0
+        out = np.zeros(max(n, 0), np.int64)
+        self._check(self.L.sbam_get_sort_order(self.ctx, i0, n, _ptr(out)))
+        return out
+
     # ---- BAM writer
     def _upload(self, a: np.ndarray) -> int:
         """A device copy of a host array, allocated through the HIP runtime libsbam.so is linked to (dlsym through the
@@ -1007,13 +1047,17 @@ class BamFile:
 
     def write_bam(self, path: Optional[str] = None, ranges: Optional[Sequence[Tuple[int, int]]] = None, keep=None,
                   level: int = 1, block_bytes: int = WRITE_BLOCK_BYTES, with_header: bool = True,
-                  with_eof: bool = True, huffman: str = "fixed"):
+                  with_eof: bool = True, huffman: str = "fixed", order=None, header: Optional[bytes] = None):
         """The records of the last load_records back into BGZF bytes on the GPU (sbam_write_bam; htsjdk-rewrite,
         HTSJDKRewrite.scala:21-91): the BAM header, then the records inside `ranges` (record-index pairs [lo, hi),
         ascending and disjoint; None: all) whose `keep` byte is nonzero (a torch bool / uint8 tensor on this device, or
         a numpy array, which is uploaded; None: all), cut every `block_bytes`, deflated at `level` (0 stored, 1 LZ77 +
         Huffman codes: `huffman` = "fixed", or "dynamic" for per block the smallest of stored, fixed and dynamic,
-        level | SBAM_WRITE_DYNAMIC) and framed.  Returns the totals as a dict; the file bytes go to `path`, or with
+        level | SBAM_WRITE_DYNAMIC) and framed.  `order` (sbam_write_bam_ordered): "sorted" writes them in the order of
+        the last sort_records; an int64 torch tensor on this device or a numpy array (uploaded) of n_loaded entries
+        writes loaded record order[k] k-th (ranges and keep still select by loaded index; a repeated entry is written
+        twice).  `header`: the bytes of a complete BAM header written instead of the file's (sam.header_with_sort_order).
+        Returns the totals as a dict; the file bytes go to `path`, or with
         path=None into the dict as "bytes"."""
         if huffman not in ("fixed", "dynamic"):
             raise ValueError(f"huffman is 'fixed' or 'dynamic', not {huffman!r}")
@@ -1037,15 +1081,40 @@ class BamFile:
                 keep = keep.contiguous()
                 torch.cuda.synchronize(keep.device)
                 keep_ptr = keep.data_ptr()
+        ordered = order is not None or header is not None
+        order_ptr, staged_order = None, None
+        if order is not None and not (isinstance(order, str) and order == "sorted"):
+            if isinstance(order, str):
+                raise ValueError(f"order is 'sorted', a tensor or an array, not {order!r}")
+            if int(np.prod(order.shape)) != self.n_loaded:
+                raise ValueError(f"order has {int(np.prod(order.shape))} entries for {self.n_loaded} loaded records")
+            if isinstance(order, np.ndarray):
+                staged_order = order_ptr = self._upload(np.ascontiguousarray(order).astype(np.int64))
+            else:
+                import torch
+                if not order.is_cuda or order.device.index != self.device or order.dtype != torch.int64:
+                    raise ValueError("order: an int64 tensor on this BamFile's device, or a numpy array")
+                order = order.contiguous()
+                torch.cuda.synchronize(order.device)
+                order_ptr = order.data_ptr()
+        elif order is None and ordered:  # a header alone: the loaded order
+            staged_order = order_ptr = self._upload(np.arange(self.n_loaded, dtype=np.int64))
+        hbuf = np.frombuffer(bytes(header), np.uint8) if header is not None else None
+        o = _WriteOrder(order_ptr, _ptr(hbuf) if hbuf is not None and hbuf.size else None,
+                        hbuf.size if hbuf is not None else 0)
         a = _WriteArgs(_ptr(lo) if lo.size else None, _ptr(hi) if hi.size else None, lo.size,
                        keep_ptr if self.n_loaded else None, int(level), int(block_bytes), 1 if with_header else 0,
                        1 if with_eof else 0)
         t = _WriteTotals()
         try:
-            rc = self.L.sbam_write_bam(self.ctx, ctypes.byref(a), ctypes.byref(t))
+            if ordered:
+                rc = self.L.sbam_write_bam_ordered(self.ctx, ctypes.byref(a), ctypes.byref(o), ctypes.byref(t))
+            else:
+                rc = self.L.sbam_write_bam(self.ctx, ctypes.byref(a), ctypes.byref(t))
         finally:
-            if staged:
-                self.L.hipFree(ctypes.c_void_p(staged))
+            for q in (staged, staged_order):
+                if q:
+                    self.L.hipFree(ctypes.c_void_p(q))
         self._check(rc)
         out = {k: int(getattr(t, k)) for k, _ in _WriteTotals._fields_}
         self._written = out

@@ -12,6 +12,7 @@
     python -m sbam.cli tags -t NM,RG,MD [-m SPLIT] [--verify-crc] BAM [OUT]
     python -m sbam.cli index-bam [-o OUT] [--allow-unsorted] [--verify-crc] [-m SPLIT] BAM
     python -m sbam.cli check-crc [-l LIMIT] [--windows W] BAM [OUT]
+    python -m sbam.cli sort -o OUT [--level 0|1] [--huffman fixed|dynamic] [--index] [-m SPLIT] BAM
 
 Report text follows the reference apps line for line, so the goldens of cli/src/test/resources/output/ diff
 verbatim (tests/test_cli.py):
@@ -34,6 +35,9 @@ verbatim (tests/test_cli.py):
   * check-crc: every BGZF block's CRC32 against its footer (no reference counterpart: Stream.scala:49-54 never reads
     it; what `bgzip -t` checks), computed on the GPU by sbam_check_crc; --verify-crc makes view and index-bam check it
     while they load.
+  * sort: the records in coordinate order (no reference counterpart; htsjdk's SortOrder.coordinate writer, `samtools
+    sort` without its strand tie-break), sorted on the GPU by sbam_sort_records and written by sbam_write_bam_ordered
+    behind a header with SO:coordinate.
 Counting, checking and splitting all run through libsbam.so (sbam.BamFile); this module only formats."""
 from __future__ import annotations
 
@@ -807,6 +811,29 @@ def rewrite_main(a) -> int:
     return 0
 
 
+# ---- sort ----------------------------------------------------------------------------------------------------
+def sort_main(a) -> int:
+    """IN's records in coordinate order into OUT (what `samtools sort` and htsjdk's SortOrder.coordinate writer leave,
+    ties in file order): load every record, sort on the GPU, write in that order behind the header with SO:coordinate;
+    --index then reopens OUT and writes OUT.bai.  One line: records, out-of-order records before the sort, radix
+    passes, blocks."""
+    from sbam import sam
+    data = open(a.bam, "rb").read()
+    with sbam.BamFile(data, path=a.bam) as f:
+        f.load_records(sbam.effective_split_size(a.max_split_size), columns=None)
+        t = f.sort_records()
+        w = f.write_bam(a.out, level=a.level, huffman=a.huffman, order="sorted",
+                        header=sam.header_with_sort_order(f.header_bytes(), "coordinate"))
+    if a.index:
+        with sbam.BamFile(open(a.out, "rb").read(), path=a.out) as g:
+            bai = g.build_bai(sbam.effective_split_size(a.max_split_size))
+        with open(a.out + ".bai", "wb") as fh:
+            fh.write(bai)
+    print(f"{t['n_records']} records, {t['n_out_of_order']} out of order before the sort, {t['passes']} passes, "
+          f"{w['n_blocks']} blocks")
+    return 0
+
+
 # ---- check-crc ---------------------------------------------------------------------------------------------
 def check_crc_lines(n_blocks: int, n_bytes: int, bad: Sequence[Tuple[int, int, int]], limit: int) -> List[str]:
     """The check-crc report: blocks and uncompressed bytes checked, then `All CRC32s match` or the mismatching blocks
@@ -886,6 +913,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     p.add_argument("-m", "--max-split-size", type=parse_bytes, default=None)
     p.add_argument("bam")
     p.add_argument("out")
+    p = sub.add_parser("sort")
+    p.add_argument("-o", "--out", required=True)
+    p.add_argument("--level", type=_level_arg, default=1, help="0 stored, 1 LZ77 + Huffman codes (--huffman)")
+    p.add_argument("--huffman", choices=("fixed", "dynamic"), default="fixed",
+                   help="level 1's codes: the fixed one, or per block the smallest of stored, fixed and dynamic")
+    p.add_argument("--index", action="store_true", help="write OUT.bai")
+    p.add_argument("-m", "--max-split-size", type=parse_bytes, default=None)
+    p.add_argument("bam")
     for name in ("full-check", "check-bam", "check-blocks", "compute-splits", "count-reads", "index-blocks",
                  "index-records"):
         p = sub.add_parser(name)
@@ -917,6 +952,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         return index_bam_main(a)
     if a.cmd == "check-crc":
         return check_crc_main(a)
+    if a.cmd == "sort":
+        if a.huffman == "dynamic" and a.level == 0:
+            ap.error("--huffman dynamic needs --level 1: level 0 writes stored blocks only")
+        return sort_main(a)
     if a.cmd == "htsjdk-rewrite":
         if a.huffman == "dynamic" and a.level == 0:
             ap.error("--huffman dynamic needs --level 1: level 0 writes stored blocks only")

@@ -159,3 +159,30 @@ def sam_lines(columns: Dict[str, np.ndarray], fields, contig_names: Sequence[str
         cols += tag_texts(auxs[ao[k]:ao[k + 1]])
         out.append("\t".join(cols))
     return out
+
+
+def header_with_sort_order(header_bytes: bytes, order: str = "coordinate") -> bytes:
+    """A complete BAM header (magic, l_text, text, n_ref, the references) with `SO:<order>` on its `@HD` line (SAM spec
+    §1.3), as htsjdk's SAMFileHeader.setSortOrder and `samtools sort` leave it: the `SO:` field of an `@HD` first line
+    is replaced, or `\\tSO:<order>` appended to it; a text without `@HD` gets `@HD\\tVN:1.6\\tSO:<order>\\n` in front.
+    Trailing NUL padding of the text is dropped, l_text follows, and the reference list is kept byte for byte.  Host
+    only."""
+    h = bytes(header_bytes)
+    if len(h) < 12 or h[:4] != b"BAM\x01":
+        raise ValueError("not a BAM header: no magic")
+    (l_text,) = struct.unpack_from("<i", h, 4)
+    if l_text < 0 or 8 + l_text + 4 > len(h):
+        raise ValueError("not a BAM header: l_text runs past its end")
+    text, refs = h[8:8 + l_text].rstrip(b"\0"), h[8 + l_text:]
+    so = b"SO:" + order.encode("ascii")
+    if text.startswith(b"@HD\t") or text.split(b"\n", 1)[0] == b"@HD":
+        line, nl, rest = text.partition(b"\n")
+        fields = line.split(b"\t")
+        if any(f.startswith(b"SO:") for f in fields[1:]):
+            fields = [fields[0]] + [so if f.startswith(b"SO:") else f for f in fields[1:]]
+        else:
+            fields.append(so)
+        text = b"\t".join(fields) + nl + rest
+    else:
+        text = b"@HD\tVN:1.6\t" + so + b"\n" + text
+    return h[:4] + struct.pack("<i", len(text)) + text + refs
