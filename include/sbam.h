@@ -204,8 +204,18 @@ int sbam_set_contig_lengths(sbam_ctx *ctx, int32_t n_ref, const int64_t *lengths
 
 /* ---- record-boundary checkers --------------------------------------------------------------- */
 
+/* Shards.  A context opened with base_offset + len < file_size holds a stream that ends (at L) before the file does.
+ * There every function below answers what the whole file would answer, or HALO: a position, search or chain that
+ * needed a byte at or past L (a record's fixed bytes, name or CIGAR ops, or a hop offset + 4 + block_size > L) is
+ * unknown, never decided from the bytes at hand.  HALO is SBAM_WORD_HALO in the words, n_halo / SBAM_ERR_HALO from the
+ * counts (the other fields are the reductions over the decided positions), and SBAM_ERR_HALO from the record search
+ * and the split functions.  The caller loads a longer range and asks again; no other error asks for that. */
+
 /* eager.Checker at every uncompressed offset in [x0, x1) (check/.../check/eager/Checker.scala:24-126):
- * bit i of bitmap (LSB-first within uint64 words) = call at x0+i.  bitmap may be NULL (device-only). */
+ * bit i of bitmap (LSB-first within uint64 words) = call at x0+i.  bitmap may be NULL (device-only).
+ * On a shard the bit of an unknown position is 0, like a failure's, and the call still returns SBAM_OK; the context
+ * remembers the smallest unknown position and lets the bitmap stand for [x0, that position) only, so that
+ * sbam_find_record_start and the split functions decide the rest themselves (and answer HALO there). */
 int sbam_check_eager(sbam_ctx *ctx, int64_t x0, int64_t x1, int32_t reads_to_check, uint64_t *bitmap);
 
 /* full.Checker result words for [x0, x1) (check/.../check/full/Checker.scala:22-184). */
@@ -219,7 +229,8 @@ int sbam_check_full_counts(sbam_ctx *ctx, int64_t x0, int64_t x1, int32_t reads_
                            sbam_counts *counts, uint64_t *success_bitmap);
 
 /* FindRecordStart.withDelta (check/.../bam/spark/FindRecordStart.scala:30-63) from Pos(block_start, 0):
- * *found = 0 means None. */
+ * *found = 0 means None.  On a shard: the first position, in order, that is Success or unknown decides; unknown, or
+ * reaching the stream's end with attempts left, is SBAM_ERR_HALO. */
 int sbam_find_record_start(sbam_ctx *ctx, int64_t block_start, int32_t reads_to_check, int32_t max_read_size,
                            int32_t *found, sbam_pos *pos, int32_t *delta);
 
@@ -239,7 +250,9 @@ int sbam_file_splits(int64_t file_size, int64_t split_size, int64_t *starts, int
 
 /* For Hadoop splits [first, first+count) of the file: FindBlockStart → FindRecordStart → record chain
  * with Pos < (end, 0).  Writes each split's first-record position (found[i]=0 when the split is empty or
- * past the shard) and record count (= the partition size of loadReads / loadReadsAndPositions). */
+ * past the shard) and record count (= the partition size of loadReads / loadReadsAndPositions).
+ * On a shard SBAM_ERR_HALO when a first-record search or a chain needed bytes past the stream's end, or when no
+ * loaded block starts at or past a split's end and the loaded blocks end before it. */
 int sbam_split_records(sbam_ctx *ctx, const sbam_split_args *args, int64_t first, int64_t count, sbam_pos *first_pos,
                        int32_t *found, int64_t *n_records);
 

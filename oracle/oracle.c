@@ -427,3 +427,118 @@ int64_t or_find_record_start_window(const uint8_t *u, int64_t L, const int64_t *
   }
   return -1;
 }
+
+/* ------------------------------------------------------------------------------------------------
+ * Per-position window forms: what a context opened on a byte range of the file (a shard) may answer.
+ * u[0..L) is a slice of the whole file's stream that ends before the file does.  A position whose
+ * evaluation tested `> L` (hit) is unknown there: the bytes past L decide it.  Every other position's
+ * result is the whole file's.
+ * ---------------------------------------------------------------------------------------------- */
+
+void or_check_full_window(const uint8_t *u, int64_t L, const int64_t *lens, int32_t nref, int64_t p0, int64_t p1,
+                          int32_t R, uint32_t *words, uint8_t *hits) {
+  for (int64_t p = p0; p < p1; p++) {
+    int hit = 0;
+    words[p - p0] = check_full_core(u, L, lens, nref, p, R, &hit);
+    hits[p - p0] = (uint8_t)hit;
+  }
+}
+
+/* eager.Checker.apply (eager/Checker.scala:24-126) in its own order of tests: the fixed block (:32-42), then every
+ * test on the fixed fields (:49-77), then the name's read and bytes (:81-95), then the CIGAR ops one read at a time
+ * (:97-109), then the skip to the next record (:116-119).  *hit is set only when one of its reads or the skip met L
+ * before it returned: a record that fails a fixed-field test never reads its name, so its hits are a subset of the
+ * full checker's. */
+static inline int check_eager_core(const uint8_t *u, int64_t L, const int64_t *lens, int32_t nref, int64_t p, int32_t R,
+                                   int *hit) {
+  int64_t s = p, a = p;
+  for (int32_t k = 0;; k++) {
+    if (k == R) return 1;
+    if (a + 36 > L) {
+      *hit = 1;
+      return k > 0 && s == L;
+    }
+    int32_t bs = i32le(u, a), ri = i32le(u, a + 4), rp = i32le(u, a + 8), bmn = i32le(u, a + 12);
+    int32_t fnc = i32le(u, a + 16), ls = i32le(u, a + 20), nri = i32le(u, a + 24), nrp = i32le(u, a + 28);
+    if (ref_err(ri, rp, lens, nref)) return 0;
+    int32_t lrn = bmn & 0xff;
+    if (lrn < 2) return 0;
+    uint32_t flag = ((uint32_t)fnc) >> 16;
+    int32_t nc = fnc & 0xffff;
+    if ((flag & 4u) == 0 && (ls == 0 || nc == 0)) return 0;
+    int32_t t = (int32_t)((uint32_t)ls + 1u);
+    int32_t nsq = (int32_t)((uint32_t)(t / 2) + (uint32_t)ls);
+    if (bs < (int32_t)(32u + (uint32_t)lrn + 4u * (uint32_t)nc + (uint32_t)nsq)) return 0;
+    if (ref_err(nri, nrp, lens, nref)) return 0;
+    int64_t c = a + 36;
+    if (c + lrn > L) {
+      *hit = 1;
+      return 0;
+    }
+    if (u[c + lrn - 1] != 0) return 0;
+    for (int32_t i = 0; i < lrn - 1; i++)
+      if (!name_char_ok(u[c + i])) return 0;
+    c += lrn;
+    for (int32_t i = 0; i < nc; i++) {
+      if (c + 4 > L) {
+        *hit = 1;
+        return 0;
+      }
+      uint8_t op = u[c];
+      c += 4;
+      if ((op & 0xf) > 8) return 0;
+    }
+    int64_t nxt = s + 4 + (int64_t)bs;
+    if (nxt > L) *hit = 1;
+    a = nxt > c ? (nxt > L ? L : nxt) : c;
+    s = nxt;
+  }
+}
+
+void or_check_eager_window(const uint8_t *u, int64_t L, const int64_t *lens, int32_t nref, int64_t p0, int64_t p1,
+                           int32_t R, uint8_t *calls, uint8_t *hits) {
+  for (int64_t p = p0; p < p1; p++) {
+    int hit = 0;
+    calls[p - p0] = (uint8_t)check_eager_core(u, L, lens, nref, p, R, &hit);
+    hits[p - p0] = (uint8_t)hit;
+  }
+}
+
+/* FindRecordStart.withDelta on a window, position by position as the reference runs it: the first p in
+ * [x0, x0 + max_read_size) whose eager call is Success or unknown decides.  Returns p (Success), -2 (unknown, or the
+ * search reached L: the next position lies past the window) or -1 (None). */
+int64_t or_find_record_start_window_eager(const uint8_t *u, int64_t L, const int64_t *lens, int32_t nref, int64_t x0,
+                                          int32_t R, int64_t max_read_size) {
+  for (int64_t i = 0; i < max_read_size; i++) {
+    int64_t x = x0 + i;
+    if (x >= L) return -2;
+    int hit = 0;
+    int ok = check_eager_core(u, L, lens, nref, x, R, &hit);
+    if (hit) return -2;
+    if (ok) return x;
+  }
+  return -1;
+}
+
+/* or_record_chain on a window: *hit when the chain needed a byte at or past L before it reached x_end (a block_size
+ * that straddles L, or a record that runs past it). */
+int64_t or_record_chain_window(const uint8_t *u, int64_t L, int64_t x0, int64_t x_end, int64_t *out, int64_t cap,
+                               int32_t *hit) {
+  int64_t n = 0, x = x0;
+  *hit = 0;
+  while (x < x_end) {
+    if (x + 4 > L) {
+      *hit = 1;
+      break;
+    }
+    int32_t bs = i32le(u, x);
+    if (x + 4 + (int64_t)bs > L) {
+      *hit = 1;
+      break;
+    }
+    if (n < cap && out) out[n] = x;
+    n++;
+    x = x + 4 + (int64_t)bs;
+  }
+  return n;
+}

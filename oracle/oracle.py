@@ -66,6 +66,14 @@ def lib():
         L.or_find_record_start.argtypes = [vp, i64, vp, i32, i64, i32, i64]
         L.or_record_chain.restype = i64
         L.or_record_chain.argtypes = [vp, i64, i64, i64, vp, i64]
+        L.or_check_full_window.restype = None
+        L.or_check_full_window.argtypes = [vp, i64, vp, i32, i64, i64, i32, vp, vp]
+        L.or_check_eager_window.restype = None
+        L.or_check_eager_window.argtypes = [vp, i64, vp, i32, i64, i64, i32, vp, vp]
+        L.or_find_record_start_window_eager.restype = i64
+        L.or_find_record_start_window_eager.argtypes = [vp, i64, vp, i32, i64, i32, i64]
+        L.or_record_chain_window.restype = i64
+        L.or_record_chain_window.argtypes = [vp, i64, i64, i64, vp, i64, vp]
         _lib = L
     return _lib
 
@@ -209,6 +217,52 @@ class BamFile:
         """Flat offset of Pos(end, 0): first block whose start >= end (records with Pos < (end,0))."""
         b = self.block_index_at_or_after(end_compressed)
         return int(self.uoff[b]) if b < self.nblocks else self.L
+
+
+# ---- window forms: a slice u = o.u[a:b] of a whole file's stream, with the whole file's contig lengths ----------
+HALO = "halo"  # what a window answers where the bytes past its end decide
+
+
+def _window(u, lens):
+    u = np.ascontiguousarray(u, np.uint8)
+    lens = np.ascontiguousarray(lens, np.int64)
+    pad = np.zeros(u.size + 64, np.uint8)  # (the C side never reads at or past L; the pad keeps a slip from faulting)
+    pad[:u.size] = u
+    return pad, int(u.size), lens
+
+
+def check_full_window(u, lens, reads_to_check: int = 10, p0: int = 0, p1=None):
+    """(words, hits) of positions [p0, p1) of the window: hits[i] says the evaluation tested a byte past the window."""
+    w, L, lens = _window(u, lens)
+    p1 = L if p1 is None else p1
+    words, hits = np.zeros(max(p1 - p0, 0), np.uint32), np.zeros(max(p1 - p0, 0), np.uint8)
+    lib().or_check_full_window(_p(w), L, _p(lens), lens.size, p0, p1, reads_to_check, _p(words), _p(hits))
+    return words, hits.astype(bool)
+
+
+def check_eager_window(u, lens, reads_to_check: int = 10, p0: int = 0, p1=None):
+    """(calls, hits) of the eager checker, in its own order of tests (its hits are a subset of the full checker's)."""
+    w, L, lens = _window(u, lens)
+    p1 = L if p1 is None else p1
+    calls, hits = np.zeros(max(p1 - p0, 0), np.uint8), np.zeros(max(p1 - p0, 0), np.uint8)
+    lib().or_check_eager_window(_p(w), L, _p(lens), lens.size, p0, p1, reads_to_check, _p(calls), _p(hits))
+    return calls.astype(bool), hits.astype(bool)
+
+
+def find_record_start_window_eager(u, lens, x0: int, reads_to_check: int = 10, max_read_size: int = 10_000_000):
+    """The window offset of the first record start from x0, None, or HALO."""
+    w, L, lens = _window(u, lens)
+    x = lib().or_find_record_start_window_eager(_p(w), L, _p(lens), lens.size, x0, reads_to_check, max_read_size)
+    return HALO if x == -2 else None if x < 0 else int(x)
+
+
+def record_chain_window(u, x0: int, x_end: int):
+    """(record offsets in [x0, x_end), whether the chain needed bytes past the window before x_end)."""
+    w, L, _ = _window(u, np.zeros(1, np.int64))
+    cap = max((min(x_end, L) - x0) // 4 + 2, 2)
+    out, hit = np.zeros(cap, np.int64), np.zeros(1, np.int32)
+    n = lib().or_record_chain_window(_p(w), L, x0, x_end, _p(out), cap, _p(hit))
+    return out[:n], bool(hit[0])
 
 
 def hadoop_splits(size: int, split_size: int):

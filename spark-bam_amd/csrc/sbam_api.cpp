@@ -212,11 +212,13 @@ struct BlockMirror {
 //   arena_used                 TokPool::arena_used
 //   crc_bad, crc_first_bad     run_crc (written and read back as one pair)
 //   order_bad                  sbam_write_bam_ordered: an entry of the caller's order outside the loaded records
+//   first_halo                 the checkers on a shard: CountsDev::first_halo
 struct Scratch {
   int64_t scan_total, scan_overflow, table_first, chain_stop, inflate_error, record_count, proof_fail, arena_used;
   int64_t crc_bad, crc_first_bad;
   int64_t follow_bad, follow_stop, follow_total;
   int64_t order_bad;
+  int64_t first_halo;
 };
 
 }  // namespace
@@ -398,9 +400,12 @@ StreamView view(sbam_ctx *c) {
 
 // ---- stage state -----------------------------------------------------------------------------------
 // What a check left in d_bitmap; dropped by whatever changes the stream or the checker's inputs under it.
-void set_bitmap(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, bool list_form) {
+// first_halo: the smallest position of [x0, x1) whose call is unknown on a shard (-1: none).  Its bit and those of
+// later unknown positions are clear like a failure's, so the bitmap counts as covering the range only below it: the
+// consumers evaluate what lies behind themselves (k_find_record_starts, split_counts' walk), and those answer HALO.
+void set_bitmap(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, bool list_form, int64_t first_halo = -1) {
   c->bm_x0 = x0 & ~(int64_t)63;
-  c->bm_x1 = x1;
+  c->bm_x1 = first_halo >= 0 && first_halo < x1 ? first_halo : x1;
   c->bm_R = R;
   c->bm_list = list_form;
   c->bm_valid = true;
@@ -1305,6 +1310,19 @@ static int check_range_args(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R) {
 static hipError_t run_chains(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, int32_t by_key, CountsDev cd,
                              bool *list_form, const int32_t *tile_pass0 = nullptr);
 
+// CountsDev::first_halo for a check of this context: the scratch word set to "none" on a shard, nullptr on a whole file.
+static hipError_t first_halo_begin(sbam_ctx *c, unsigned long long **out) {
+  *out = nullptr;
+  if (view(c).eof_real) return hipSuccess;
+  *out = USMALL(c, first_halo);
+  return hipMemsetAsync(*out, 0xff, 8, c->stream);
+}
+// ... and its value once the check has run (-1: none); the caller synchronises the stream before it reads *out.
+static hipError_t first_halo_fetch(sbam_ctx *c, const unsigned long long *d, int64_t *out) {
+  *out = -1;
+  return d ? hipMemcpyAsync(out, d, 8, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+}
+
 int sbam_check_eager(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, uint64_t *bitmap) {
   if (!c) return SBAM_ERR_ARG;
   int rc = check_range_args(c, x0, x1, R);
@@ -1313,20 +1331,24 @@ int sbam_check_eager(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, uint64_t *b
   HIPCHK(c, drop_from(c, kBitmap));
   HIPCHK(c, ensure_bitmap(c, x0, x1));
   bool list_form = false;
+  CountsDev cd{};
+  int64_t first_halo = -1;
+  HIPCHK(c, first_halo_begin(c, &cd.first_halo));
   {
     Timer t(c, "check_eager");
     {
       Timer t0(c, "check_eager_pass0");
-      HIPCHK(c, launch_check_eager_pass0(view(c), x0, x1, R, c->d_bitmap, c->stream));
+      HIPCHK(c, launch_check_eager_pass0(view(c), x0, x1, R, c->d_bitmap, cd.first_halo, c->stream));
     }
-    HIPCHK(c, run_chains(c, x0, x1, R, 0, CountsDev{}, &list_form));
+    HIPCHK(c, run_chains(c, x0, x1, R, 0, cd, &list_form));
   }
+  HIPCHK(c, first_halo_fetch(c, cd.first_halo, &first_halo));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (bitmap) {
     int rc2 = copy_bitmap_out(c, x0, x1, bitmap);
     if (rc2) return rc2;
   }
-  set_bitmap(c, x0, x1, R, list_form);
+  set_bitmap(c, x0, x1, R, list_form, first_halo);
   return SBAM_OK;
 }
 
@@ -1339,13 +1361,17 @@ int sbam_check_full_words(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, uint32
   DevBuf<uint32_t> d_w;  // (per-call: one word per position)
   HIPCHK(c, d_w.ensure(x1 - x0));
   HIPCHK(c, ensure_bitmap(c, x0, x1));
+  unsigned long long *d_fh = nullptr;
+  int64_t first_halo = -1;
+  HIPCHK(c, first_halo_begin(c, &d_fh));
   {
     Timer t(c, "check_words");
-    HIPCHK(c, launch_check_words(view(c), x0, x1, R, d_w, c->d_bitmap, c->stream));
+    HIPCHK(c, launch_check_words(view(c), x0, x1, R, d_w, c->d_bitmap, d_fh, c->stream));
   }
   if (x1 > x0) HIPCHK(c, hipMemcpyAsync(words, d_w, (x1 - x0) * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, first_halo_fetch(c, d_fh, &first_halo));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  set_bitmap(c, x0, x1, R, false);
+  set_bitmap(c, x0, x1, R, false, first_halo);
   return SBAM_OK;
 }
 
@@ -1387,6 +1413,8 @@ int sbam_check_full_counts(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, int32
   cd.tile_pass0 = c->d_tcnt;
   const size_t words = cd.totals + SBAM_NUM_FLAGS - cd.counts;  // (one run)
   HIPCHK(c, hipMemsetAsync(cd.counts, 0, words * 8, c->stream));
+  int64_t first_halo = -1;
+  HIPCHK(c, first_halo_begin(c, &cd.first_halo));
   bool tiles = false, list_form = false;
   {
     Timer t(c, "check_full");
@@ -1399,6 +1427,7 @@ int sbam_check_full_counts(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, int32
   }
   std::vector<unsigned long long> hw(words);
   HIPCHK(c, hipMemcpyAsync(hw.data(), cd.counts, words * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, first_halo_fetch(c, cd.first_halo, &first_halo));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (bitmap) {
     int rc2 = copy_bitmap_out(c, x0, x1, bitmap);
@@ -1417,7 +1446,7 @@ int sbam_check_full_counts(sbam_ctx *c, int64_t x0, int64_t x1, int32_t R, int32
   out->n_success = (int64_t)h.scalars[1];
   out->n_too_few_fixed = (int64_t)h.scalars[2];
   out->n_halo = (int64_t)h.scalars[3];
-  set_bitmap(c, x0, x1, R, list_form);
+  set_bitmap(c, x0, x1, R, list_form, first_halo);
   if (out->n_halo) {
     c->err.actual = out->n_halo;
     return set_err(c, SBAM_ERR_HALO, "%lld positions need bytes past the shard", (long long)out->n_halo);
@@ -1522,6 +1551,10 @@ static int split_starts(sbam_ctx *c, const sbam_split_args *a, int64_t first, in
       return no_read_found(c, bs[i], a->max_read_size);
     }
     x0[i] = buo[b];
+    // On a shard the first block at or past the split's end may lie behind the loaded blocks; only when they end at or
+    // past the split's end is it the block that follows them, whose Pos(start, 0) is the stream's end.
+    if (ie >= nbh && !view(c).eof_real && (nbh == 0 || bst[nbh - 1] + c->blk.csize[nbh - 1] < qe))
+      return set_err(c, SBAM_ERR_HALO, "the block at the split's end lies past the shard");
     xe[i] = ie < nbh ? buo[ie] : c->L;  // flat offset of Pos(first block starting at or past the end, 0)
   }
   rc = find_record_starts(c, x0, a->reads_to_check, a->max_read_size, a->use_success_bitmap != 0, xs);

@@ -213,6 +213,11 @@ SB_DEV uint32_t walk_chain(const StreamView &sv, const unsigned long long *bitma
   }
 }
 
+// A chain whose call is unknown on a shard: the bitmap covers the range only below the smallest such position.
+SB_DEV void note_halo(const CountsDev &cd, uint32_t w, int64_t p) {
+  if (w == W_HALO && cd.first_halo) atomicMin(cd.first_halo, (unsigned long long)p);
+}
+
 SB_DEV void count_chain_result(const CountsDev &cd, uint32_t w, bool bykey) {
   if (w == W_HALO) { atomicAdd(&cd.scalars[3], 1ull); return; }
   if (w & W_SUCC) return;
@@ -282,6 +287,7 @@ __global__ __launch_bounds__(256) void k_chains(StreamView sv, int64_t x0, int64
         const uint32_t w = walk_chain(sv, bitmap, x0a, x1, p, R);
         if (w & W_SUCC) n_succ++;
         else atomicAnd(&bitmap[(p - x0a) >> 6], ~(1ull << ((p - x0a) & 63)));
+        note_halo(cd, w, p);
         if (cd.counts) count_chain_result(cd, w, bykey != 0);
         if (words) words[p - x0] = w;
       }
@@ -380,9 +386,14 @@ __global__ __launch_bounds__(256) void k_p0_links(StreamView sv, const int64_t *
     const int32_t nc = (int32_t)((uint32_t)sv.u[p + 16] | ((uint32_t)sv.u[p + 17] << 8));
     const int64_t c_end = p + 36 + (lrn >= 2 ? lrn : 0) + 4 * (int64_t)nc;
     const int64_t nxt = p + 4 + (int64_t)bs;
-    const bool link = i + 1 < n ? list[i + 1] == nxt : (nxt >= x1 && nxt <= sv.L);
+    bool link = i + 1 < n ? list[i + 1] == nxt : (nxt >= x1 && nxt <= sv.L);
+    // On a shard a record's call is unknown as soon as a record of its chain hops past the last byte, the R-th one
+    // included (walk_chain): the link to such a record does not hold, so every call that would rest on it is walked.
+    if (link && !sv.eof_real && i + 1 < n) link = nxt + 4 + (int64_t)g_i32(sv.u, nxt) <= sv.L;
     // (nxt == c_end, a record that ends with its name and CIGAR, leaves walk_chain's cursor on nxt as well)
-    ok[i] = (link && nxt >= c_end) ? 1 : 0;
+    // bit 1: the hop passes a shard's last byte, so that even the one-record call (R = 1, which needs no link) is
+    // unknown, as walk_chain says (no link holds then: bit 0 is clear)
+    ok[i] = ((link && nxt >= c_end) ? 1 : 0) | ((nxt > sv.L && !sv.eof_real) ? 2 : 0);
   }
 }
 
@@ -396,11 +407,12 @@ __global__ __launch_bounds__(256) void k_p0_fast(const int64_t *__restrict__ lis
   const int64_t n = *n_ptr;
   uint32_t n_succ = 0, n_gap = 0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    bool succ = i + (R - 1) <= n - 1 || R <= 1;
-    for (int k = 0; succ && k < R - 1; k++) succ = ok[i + k] != 0;
+    // (R = 1 needs no link, only a hop that stays inside a shard's bytes; R = 0 nothing)
+    bool succ = R == 1 ? !(ok[i] & 2) : (i + (R - 1) <= n - 1 || R <= 0);
+    for (int k = 0; succ && k < R - 1; k++) succ = (ok[i + k] & 1) != 0;
     if (succ) n_succ++;
     else fb[atomicAdd(n_fb, 1ull)] = list[i];
-    n_gap += !ok[i] ? 1u : 0u;
+    n_gap += !(ok[i] & 1) ? 1u : 0u;
   }
   if (__ballot(n_gap != 0)) {
     n_gap = wave_sum(n_gap);
@@ -420,7 +432,7 @@ __global__ __launch_bounds__(256) void k_p0_fast16(const int64_t *__restrict__ l
   const int64_t n = *n_ptr;
   const uint32_t need = (1u << (R - 1)) - 1u;  // R - 1 consecutive links
   uint32_t n_succ = 0, n_gap = 0;
-  auto nib = [](uint32_t w) { return (((w & 0x01010101u) * 0x00204081u) >> 21) & 0xfu; };  // byte k != 0 -> bit k
+  auto nib = [](uint32_t w) { return (((w & 0x01010101u) * 0x00204081u) >> 21) & 0xfu; };  // bit 0 of byte k -> bit k (bit 1 of ok[]: k_p0_links)
   for (int64_t i0 = 16 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x); i0 < n;
        i0 += 16 * (int64_t)gridDim.x * blockDim.x) {
     uint32_t m = 0;
@@ -429,7 +441,7 @@ __global__ __launch_bounds__(256) void k_p0_fast16(const int64_t *__restrict__ l
       const uint2 b = *reinterpret_cast<const uint2 *>(ok + i0 + 16);
       m = nib(a.x) | nib(a.y) << 4 | nib(a.z) << 8 | nib(a.w) << 12 | nib(b.x) << 16 | nib(b.y) << 20;
     } else {
-      for (int k = 0; k < 24 && i0 + k < n; k++) m |= (ok[i0 + k] != 0 ? 1u : 0u) << k;
+      for (int k = 0; k < 24 && i0 + k < n; k++) m |= (uint32_t)(ok[i0 + k] & 1) << k;
     }
 #pragma unroll
     for (int j = 0; j < 16; j++) {
@@ -467,6 +479,7 @@ __global__ __launch_bounds__(256) void k_p0_fallback(StreamView sv, int64_t x0a,
       atomicAnd(&bitmap[(p - x0a) >> 6], ~(1ull << ((p - x0a) & 63)));
       atomicAdd(&n_fb[2], 1ull);
     }
+    note_halo(cd, w, p);
     if (cd.counts) count_chain_result(cd, w, bykey != 0);
   }
   if (cd.counts) {
@@ -1002,6 +1015,8 @@ __global__ __launch_bounds__(kCheckThreads, kCheckWgs) void k_check(
   __shared__ uint32_t s_pair[19 * 19];  // close-call pairs (key 2)
   __shared__ int32_t s_nxt[4 * kNxt];   // long op arrays (stage_nxt)
   __shared__ int64_t s_pw[4][4];        // ... past the window, per wave and class (first_bad_op)
+  __shared__ unsigned long long s_fh;   // smallest HALO position of this workgroup's tiles (CountsDev::first_halo)
+  if (threadIdx.x == 0) s_fh = ~0ull;
   const int lane = lane_id();
   for (int i = threadIdx.x; i < 3 * 19; i += kCheckThreads) s_k12[i] = 0;
   for (int i = threadIdx.x; i < 19 * 19; i += kCheckThreads) s_pair[i] = 0;
@@ -1053,7 +1068,10 @@ __global__ __launch_bounds__(kCheckThreads, kCheckWgs) void k_check(
 #pragma unroll
         for (int q = 0; q < 8; q++) f[q] = o == 0 ? (int32_t)W[q] : (int32_t)__builtin_amdgcn_alignbyte(W[q + 1], W[q], o);
         uint32_t w = check_first<EAGER, INTERIOR>(tl, sv, lensL, x, 4 * g + o, R, f);
-        if (!INTERIOR) w = (x >= x0 && x < x1) ? w : W_NONE;  // interior tiles lie inside [x0, x1)
+        if (!INTERIOR) {
+          w = (x >= x0 && x < x1) ? w : W_NONE;  // interior tiles lie inside [x0, x1)
+          if (w == W_HALO) atomicMin(&s_fh, (unsigned long long)x);  // (a shard's last tiles only)
+        }
         wd[o] = w;
       }
       if (MODE == MODE_WORDS) {
@@ -1106,6 +1124,10 @@ __global__ __launch_bounds__(kCheckThreads, kCheckWgs) void k_check(
         since_flush = 0;
       }
     }
+  }
+  if (cd.first_halo) {
+    __syncthreads();
+    if (threadIdx.x == 0 && s_fh != ~0ull) atomicMin(cd.first_halo, s_fh);
   }
   if (COUNTS) {
     flush_acc(acc, s_acc, lane);
@@ -1739,10 +1761,9 @@ __global__ __launch_bounds__(kCheckThreads) void k_find_record_starts(StreamView
                                                                       const unsigned long long *__restrict__ bitmap,
                                                                       int64_t bx0, int64_t bx1,
                                                                       int64_t *__restrict__ out) {
-  __shared__ unsigned long long s_best;
-  __shared__ int s_halo;
+  __shared__ unsigned long long s_best, s_halo;  // smallest Success / smallest unknown position met
   const int64_t x0 = xs[blockIdx.x];
-  if (threadIdx.x == 0) { s_best = ~0ull; s_halo = 0; }
+  if (threadIdx.x == 0) { s_best = ~0ull; s_halo = ~0ull; }
   __syncthreads();
   if (x0 < 0) {
     if (threadIdx.x == 0) out[blockIdx.x] = -1;
@@ -1769,18 +1790,27 @@ __global__ __launch_bounds__(kCheckThreads) void k_find_record_starts(StreamView
     }
     x = blim;
   }
-  while (s_best == ~0ull && x < lim && !s_halo) {
+  // The reference tries position after position, so the first position that is Success or unknown decides: an unknown
+  // one below the step's first Success is HALO, not that Success.  (The step's verdict is read between two barriers,
+  // the next step's atomics come behind the second.)
+  for (;;) {
+    const bool go = s_best == ~0ull && s_halo == ~0ull && x < lim;
+    __syncthreads();
+    if (!go) break;
     const int64_t p = x + threadIdx.x;
     if (p < lim) {
       const uint32_t word = check_chain<true>(sv, GlobalBytes{sv.u}, p, p, 0, R);
-      if (word == W_HALO) s_halo = 1;
+      if (word == W_HALO) atomicMin(&s_halo, (unsigned long long)p);
       else if (word & W_SUCC) atomicMin(&s_best, (unsigned long long)p);
     }
     __syncthreads();
     x += kCheckThreads;
   }
-  __syncthreads();
-  if (threadIdx.x == 0) out[blockIdx.x] = (s_best != ~0ull) ? (int64_t)s_best : (s_halo ? -2 : -1);
+  if (threadIdx.x == 0) {
+    // a shard's search that ran into the stream's end has positions left to try in the bytes behind it
+    const bool ran_out = !sv.eof_real && x0 + max_read_size > sv.L;
+    out[blockIdx.x] = s_halo < s_best ? -2 : s_best != ~0ull ? (int64_t)s_best : ran_out ? -2 : -1;
+  }
 }
 
 // ---- record chain ------------------------------------------------------------------------------------------
@@ -1916,7 +1946,7 @@ hipError_t launch_chain_list_run(StreamView sv, int64_t x0, int64_t x1, int32_t 
   return hipGetLastError();
 }
 hipError_t launch_check_eager_pass0(StreamView sv, int64_t x0, int64_t x1, int32_t R, unsigned long long *bitmap,
-                                    hipStream_t s) {
+                                    unsigned long long *first_halo, hipStream_t s) {
   if (x1 <= x0) return hipSuccess;
   int64_t tlo, thi;
   interior_tiles(sv, x0, x1, &tlo, &thi);
@@ -1926,17 +1956,21 @@ hipError_t launch_check_eager_pass0(StreamView sv, int64_t x0, int64_t x1, int32
     const int64_t g = std::max<int64_t>(1, std::min<int64_t>((ni + 10 * kEwWaves - 1) / (10 * kEwWaves), 131072));
     hipLaunchKernelGGL(k_eager_wave, dim3((unsigned)g), dim3(64 * kEwWaves), 0, s, sv, x0, (int)R, bitmap, tlo, thi);
   }
+  CountsDev cd{};
+  cd.first_halo = first_halo;
   if (nt > ni)
-    hipLaunchKernelGGL((k_check<MODE_EAGER>), dim3(check_grid(nt - ni)), dim3(kCheckThreads), 0, s, sv, x0, x1, R,
-                       CountsDev{}, bitmap, nullptr, tlo, thi);
+    hipLaunchKernelGGL((k_check<MODE_EAGER>), dim3(check_grid(nt - ni)), dim3(kCheckThreads), 0, s, sv, x0, x1, R, cd,
+                       bitmap, nullptr, tlo, thi);
   return hipGetLastError();
 }
 hipError_t launch_check_words(StreamView sv, int64_t x0, int64_t x1, int32_t R, uint32_t *words,
-                              unsigned long long *bitmap, hipStream_t s) {
+                              unsigned long long *bitmap, unsigned long long *first_halo, hipStream_t s) {
   if (x1 <= x0) return hipSuccess;
+  CountsDev cd{};
+  cd.first_halo = first_halo;
   hipLaunchKernelGGL((k_check<MODE_WORDS>), dim3(check_grid(ntiles_of(x0, x1))), dim3(kCheckThreads), 0, s, sv, x0, x1,
-                     R, CountsDev{}, bitmap, words, (int64_t)0, (int64_t)0);
-  hipLaunchKernelGGL(k_chains, dim3(chain_grid(x0, x1)), dim3(256), 0, s, sv, x0, x1, R, bitmap, CountsDev{}, 0, words);
+                     R, cd, bitmap, words, (int64_t)0, (int64_t)0);
+  hipLaunchKernelGGL(k_chains, dim3(chain_grid(x0, x1)), dim3(256), 0, s, sv, x0, x1, R, bitmap, cd, 0, words);
   return hipGetLastError();
 }
 hipError_t launch_find_record_starts(StreamView sv, const int64_t *x0, int64_t n, int32_t R, int64_t mrs,

@@ -59,6 +59,10 @@ struct CountsDev {  // mirrors sbam_counts (int64 fields) in device memory
   // [ntiles][4]: the record-0 pass's PASS0 positions per tile and wave (set only for the full counts that are not
   // by-key, which then write every tile's; the chain pass's chunk counts come from these instead of a second read of the bitmap)
   int32_t *tile_pass0 = nullptr;
+  // shards only (StreamView::eof_real == 0; nullptr on a whole file): the smallest position whose call is unknown
+  // (HALO), ~0 if none.  Set for the eager check as well, whose other pointers are null: its bitmap says "false" at
+  // such a position, so the bitmap covers the range only up to this one (set_bitmap).
+  unsigned long long *first_halo = nullptr;
 };
 
 // Device columns of decoded records (sbam_records.hip); mirrors sbam_record_columns minus the offsets.
@@ -170,10 +174,11 @@ hipError_t launch_chain_list_build(int64_t x0, int64_t x1, const unsigned long l
                                    const int32_t *tile_pass0, hipStream_t s);
 hipError_t launch_chain_list_run(StreamView sv, int64_t x0, int64_t x1, int32_t R, int32_t by_key, CountsDev cd,
                                  unsigned long long *bitmap, const ChainScratch &cs, hipStream_t s);
+// (first_halo: CountsDev::first_halo, nullptr on a whole file)
 hipError_t launch_check_eager_pass0(StreamView sv, int64_t x0, int64_t x1, int32_t R, unsigned long long *bitmap,
-                                    hipStream_t s);
+                                    unsigned long long *first_halo, hipStream_t s);
 hipError_t launch_check_words(StreamView sv, int64_t x0, int64_t x1, int32_t R, uint32_t *words,
-                              unsigned long long *bitmap, hipStream_t s);
+                              unsigned long long *bitmap, unsigned long long *first_halo, hipStream_t s);
 hipError_t launch_find_record_starts(StreamView sv, const int64_t *x0, int64_t n, int32_t R, int64_t max_read_size,
                                      const unsigned long long *bitmap, int64_t bitmap_x0, int64_t bitmap_x1,
                                      int64_t *out, hipStream_t s);

@@ -161,6 +161,47 @@ class TestLongReadsGpu:
         assert u["n_success"] == ns == s.n_records
         assert grew >= 1, "no shard needed a larger halo: the test does not reach the halo path"
 
+    def test_shard_loads_with_small_halo(self, long_file):
+        """The worlds of test_shards_with_small_halo through the load path.  A load checks no position but the splits'
+        first records and walks each chain only to its split's end, so it needs less halo than step(): over the three
+        worlds it is the 7-shard one (64 KiB splits) in which a shard has to grow; each world's partitions are exact."""
+        grew = {world: self._shard_loads(long_file, world, split_size)
+                for world, split_size in [(2, 1 << 20), (3, 256 * 1024), (7, 64 * 1024)]}
+        assert grew[7] >= 1, "no shard of the 7-shard world needed a larger halo: the test does not reach the halo path"
+
+    def _shard_loads(self, long_file, world, split_size):
+        """GpuShard.load_step / load_columns (the eager check, then load_records from its bitmap: what the streamed
+        load-reads benchmark runs) on the same shards: a first record or a record chain that needs bytes past the
+        64 KiB halo is a HaloException, which grows the halo, never a NoReadFoundException or a short partition.  The
+        partitions' sizes and record offsets are the single-file oracle's.  Returns how many shards grew."""
+        import oracle
+        from sbam import dist as sdist
+        s, d, o = long_file
+        parts = oracle.load_reads_and_positions(o, split_size)
+        plans = sdist.plan_shards(s.size, split_size, world)
+        sizes, pos, grew = [], [], 0
+        for p in plans:
+            sh = sdist.GpuShard(p, s.slice, split_size, s.contig_lengths, halo=64 * 1024)
+            try:
+                n = sh.load_step()
+                n2, cols = sh.load_columns(("offset", "block_pos", "block_off"))
+                assert n.tolist() == n2.tolist() and cols["offset"].size == int(n.sum())
+                sizes += n.tolist()
+                pos.append(np.stack([cols["block_pos"], cols["block_off"].astype(np.int64)], 1))
+                # the shard's stream starts on the block at p.lo
+                x0 = int(o.uoff[o.block_index_at_or_after(p.lo)]) if p.split_count else 0
+                want = np.concatenate([parts[i] for i in range(p.split_first, p.split_first + p.split_count)] +
+                                      [np.zeros(0, np.int64)])
+                assert np.array_equal(cols["offset"] + x0, want)
+                grew += sh.halo > 64 * 1024
+            finally:
+                sh.close()
+        assert sizes == [len(q) for q in parts]
+        flat = np.concatenate(parts)
+        b = np.searchsorted(o.uoff[1:], flat, side="right")
+        assert np.array_equal(np.concatenate(pos), np.stack([o.start[b], flat - o.uoff[b]], 1))
+        return grew
+
     @pytest.mark.parametrize("windows,split_size,prefetch", [(4, 256 * 1024, False), (6, 64 * 1024, False),
                                                           (3, 256 * 1024, True)])
     def test_window_pipe_halo_growth_reused_buffers(self, long_file, windows, split_size, prefetch):
